@@ -23,6 +23,20 @@ Other workloads (one JSON line per query; not the driver's headline line):
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload readme|scan|highcard|highcard-default|inverted|ssb]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does only what the headline figure needs: it stages the segments, plans the query (the first,
+cold execution), warms up, times --steps steps, writes the last step's outputs (--dump-outputs DIR) and prints
+the result line. --full adds everything measured or checked in runs of their own: the CPU baseline
+(--no-cpu-baseline drops it again), the re-planned and re-issued query latencies (cached_plan_ms,
+cached_plan_breakdown) and the COUNT-sum consistency check of the groups; those fields are null on a plain line.
+
+--dump-outputs DIR writes what a caller of the timed path receives after the last timed step, as float64 .npy
+files (prefix q<i>_ per query when the workload has several): keys [groups, group-by columns] (rows sorted by
+key, so two builds compare row for row; STRING keys are dictionary ids, DOUBLE keys their values, integer keys
+beyond 2^53 round), values [groups, aggregations] (final values as the library returns them),
+values_exact [groups, aggregations] (the exact integer results, COUNT and integer sums, as float64) and
+num_docs_matched [1]. More than 64 MB in all is cut to a fixed, seeded sample of the sorted rows (sample_rows
+holds their indices). Segments are generated from fixed seeds, so the inputs are identical from run to run.
 """
 from __future__ import annotations
 
@@ -173,6 +187,83 @@ def committed_traffic(query: str, kernel_info: str, rows: int):
     return None, None
 
 
+def plan_latencies(ex, query, segs, stream, ks, cold_ms, world):
+    """(--full) Host latencies of the query planned again and re-issued after its cold execution:
+    (cached_plan_ms, cached_plan_breakdown)."""
+    import torch
+    # the same query planned again while the first result is alive (compiled kernels cached, host planning
+    # redone): the plan of a concurrent identical query
+    t_c = time.perf_counter()
+    res_b = ex.execute(query, segs, stream=stream, key_space=ks)
+    res_b.groups()
+    torch.cuda.synchronize()
+    fresh_plan_ms = (time.perf_counter() - t_c) * 1e3
+    res_b.destroy()  # idle: kept by the library's prepared-plan cache
+    # a re-issued query (the earlier one finished): the prepared plan of its identity runs without planning.
+    # Issued 5 times (once when the group conversion alone is slow, e.g. ~1M groups): the median is reported,
+    # the spread beside it (a single sample caught host outliers: one SSB query at 2.5 ms for a 1.0-ms median)
+    samples = []
+    for _ in range(5 if cold_ms < 200 and world == 1 else 1):  # (the same count on every rank)
+        t_c = time.perf_counter()
+        res2 = ex.execute(query, segs, stream=stream, key_space=ks)
+        torch.cuda.synchronize()
+        t_f = time.perf_counter()
+        arrays = res2.fetch_arrays() if hasattr(res2, "fetch_arrays") else None
+        t_g = time.perf_counter()
+        if arrays is not None:  # Python conversion of the arrays already fetched (no second fetch)
+            res2.groups(arrays=arrays)
+        else:
+            res2.groups()
+        t_e = time.perf_counter()
+        samples.append({  # the re-issued query's host time: library execute (plan-cache lookup + launch),
+            "total_ms": (t_e - t_c) * 1e3,  # library fetch (device compaction + copy of the groups), conversion
+            "execute_ms": (t_f - t_c) * 1e3,
+            "fetch_ms": (t_g - t_f) * 1e3 if arrays is not None else None,
+            "python_groups_ms": (t_e - t_g) * 1e3,
+            "plan_phases_ms": res2.plan_timing() if hasattr(res2, "plan_timing") else None,
+        })
+        del arrays
+        res2.destroy()
+    med = sorted(samples, key=lambda x: x["total_ms"])[len(samples) // 2]
+    host_ms = {k: v for k, v in med.items() if k != "total_ms"}
+    host_ms["fresh_plan_ms"] = fresh_plan_ms
+    host_ms["reissued_ms_samples"] = [round(x["total_ms"], 3) for x in samples]
+    return med["total_ms"], host_ms
+
+
+DUMP_BYTES_MAX = 64 * 1000 * 1000  # all files of one --dump-outputs run together
+
+
+def dump_outputs(directory, prefix, res, arrays, matched, budget):
+    """Write one query's fetched result (QueryResult.fetch_arrays of the last timed step) under `directory` as
+    float64 .npy files of at most `budget` bytes together (see the module docstring for the layout)."""
+    import numpy as np
+    from pinot_amd.segment import DOUBLE, FLOAT
+    got, keys, vals, vals_i, _ = arrays
+    n = got.value
+    nk = len(res.qc.group_by)
+    nnat = max(len(res._native_aggs), 1)
+    karr = np.empty((n, nk), dtype=np.float64)
+    for j, t in enumerate(res._key_types):
+        col = keys[:n * nk].reshape(n, nk)[:, j]
+        karr[:, j] = col.view(np.float64) if t in (FLOAT, DOUBLE) else col
+    v = vals[:n * nnat].reshape(n, nnat)
+    vi = vals_i[:n * nnat].reshape(n, nnat).astype(np.float64)
+    if nk:  # group order is the plan's business (dense table, hash table): sort rows by key
+        order = np.lexsort(tuple(keys[:n * nk].reshape(n, nk)[:, j] for j in reversed(range(nk))))
+        karr, v, vi = karr[order], v[order], vi[order]
+    out = {"num_docs_matched": np.array([matched], dtype=np.float64)}
+    row_bytes = 8 * (nk + 2 * nnat + 1)
+    if n * row_bytes + 1024 > budget:
+        keep = np.sort(np.random.default_rng(0).choice(n, size=max((budget - 1024) // row_bytes, 1), replace=False))
+        karr, v, vi = karr[keep], v[keep], vi[keep]
+        out["sample_rows"] = keep.astype(np.float64)
+    out.update(keys=karr, values=np.ascontiguousarray(v), values_exact=vi)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(directory, prefix + name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -186,10 +277,17 @@ def main():
                     help="CPU baseline wall time per query (default 12 s; 4 s per query for multi-query workloads)")
     ap.add_argument("--cpu-threads", type=int, default=16,
                     help="host threads for the CPU baseline (the GPU box's CPU share per GPU is 16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline, the re-planned and re-issued "
+                         "query latencies, the COUNT-sum check of the groups (a plain run leaves those fields null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float64, at most 64 MB in all)")
     ap.add_argument("--check", action="store_true", help="verify one segment against the oracle")
     ap.add_argument("--query-index", type=int, default=None, help="run only this query of the workload")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under a launcher: start one rank per GPU as child processes (torchrun) before anything
@@ -269,44 +367,9 @@ def main():
         res.groups()
         torch.cuda.synchronize()
         cold_ms = (time.perf_counter() - t_c) * 1e3
-        # the same query planned again while the first result is alive (compiled kernels cached, host planning
-        # redone): the plan of a concurrent identical query
-        t_c = time.perf_counter()
-        res_b = ex.execute(query, segs, stream=stream, key_space=ks)
-        res_b.groups()
-        torch.cuda.synchronize()
-        fresh_plan_ms = (time.perf_counter() - t_c) * 1e3
-        res_b.destroy()  # idle: kept by the library's prepared-plan cache
-        # a re-issued query (the earlier one finished): the prepared plan of its identity runs without planning.
-        # Issued 5 times (once when the group conversion alone is slow, e.g. ~1M groups): the median is reported,
-        # the spread beside it (a single sample caught host outliers: one SSB query at 2.5 ms for a 1.0-ms median)
-        samples = []
-        for _ in range(5 if cold_ms < 200 and world == 1 else 1):  # (the same count on every rank)
-            t_c = time.perf_counter()
-            res2 = ex.execute(query, segs, stream=stream, key_space=ks)
-            torch.cuda.synchronize()
-            t_f = time.perf_counter()
-            arrays = res2.fetch_arrays() if hasattr(res2, "fetch_arrays") else None
-            t_g = time.perf_counter()
-            if arrays is not None:  # Python conversion of the arrays already fetched (no second fetch)
-                res2.groups(arrays=arrays)
-            else:
-                res2.groups()
-            t_e = time.perf_counter()
-            samples.append({  # the re-issued query's host time: library execute (plan-cache lookup + launch),
-                "total_ms": (t_e - t_c) * 1e3,  # library fetch (device compaction + copy of the groups), conversion
-                "execute_ms": (t_f - t_c) * 1e3,
-                "fetch_ms": (t_g - t_f) * 1e3 if arrays is not None else None,
-                "python_groups_ms": (t_e - t_g) * 1e3,
-                "plan_phases_ms": res2.plan_timing() if hasattr(res2, "plan_timing") else None,
-            })
-            del arrays
-            res2.destroy()
-        med = sorted(samples, key=lambda x: x["total_ms"])[len(samples) // 2]
-        plan_ms = med["total_ms"]
-        host_ms = {k: v for k, v in med.items() if k != "total_ms"}
-        host_ms["fresh_plan_ms"] = fresh_plan_ms
-        host_ms["reissued_ms_samples"] = [round(x["total_ms"], 3) for x in samples]
+        plan_ms = host_ms = None
+        if args.full:
+            plan_ms, host_ms = plan_latencies(ex, query, segs, stream, ks, cold_ms, world)
         scratch = None
 
         # device time of each step's plan: HIP events recorded on the plan's own stream around the execution
@@ -391,7 +454,11 @@ def main():
             log(f"warning: plan's algorithmic bytes {bpr:.4f} B/row != {bytes_per_row:.4f}")
         achieved = alg_bytes / avg_kernel_s / 1e9
 
-        groups = res.groups()
+        if args.dump_outputs and not hasattr(res, "fetch_arrays"):
+            log("error: --dump-outputs needs a result with fetch_arrays (no DISTINCTCOUNT queries)")
+            sys.exit(2)
+        arrays = res.fetch_arrays() if hasattr(res, "fetch_arrays") else None
+        groups = res.groups(arrays=arrays) if arrays is not None else res.groups()
         matched = res.num_docs_matched()
         if world > 1:
             m = torch.tensor([matched], dtype=torch.int64, device="cuda")
@@ -403,7 +470,7 @@ def main():
         # size-independent property: the merged group COUNTs add up to the docs that passed the filter
         # (diagnostic knobs that deliberately break results skip it; their lines say so in config)
         diag = sorted(k for k in os.environ if k.startswith("PINOT_AMD_DIAG_"))
-        counts_first = bool(qc.aggregations) and qc.aggregations[0].func == "COUNT" and not diag
+        counts_first = args.full and bool(qc.aggregations) and qc.aggregations[0].func == "COUNT" and not diag
         if qc.group_by and counts_first:
             # numGroupsLimit trimming drops the docs of groups a segment did not admit (they were scanned)
             total = sum(p[0] for p in groups.values())
@@ -432,9 +499,14 @@ def main():
 
         traffic, traffic_src = committed_traffic(query, res.kernel_info(), rows_per_rank)
 
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, f"q{len(outs)}_" if len(queries) > 1 else "", res, arrays, matched_all,
+                         DUMP_BYTES_MAX // len(queries))
+        del arrays
+
         if rank == 0:
             cpu = None
-            if not args.no_cpu_baseline and world == 1:
+            if args.full and not args.no_cpu_baseline and world == 1:
                 log("[rank 0] timing the CPU baseline ...")
                 cpu = cpu_baseline(args.workload, query, min(args.rows, 10_000_000), args.cpu_seconds,
                                    max(1, min(args.cpu_threads, os.cpu_count() or 1)), cpu_cache)

@@ -31,7 +31,7 @@ SETS_FULL=("FETCH_SIZE" "WRITE_SIZE"
   "SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_ANY SQ_INST_CYCLES_VMEM_WR"
   "TCP_TCC_ATOMIC_WITH_RET_REQ_sum TCP_TCC_ATOMIC_WITHOUT_RET_REQ_sum TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum")
 for w in ${WORKLOADS:-scan highcard hcdef}; do
-  A="$(args_for $w) --no-cpu-baseline"
+  A="$(args_for $w) --full --no-cpu-baseline"  # --full: the re-planned and re-issued executions summarize.py counts
   D=$OUT/$w
   mkdir -p $D
   timeout -s KILL 240 rocprofv3 --kernel-trace --stats --output-format csv -d $D/trace -o run -- python3 bench.py $A --steps 10 --warmup 2 > $D/trace_bench.json 2> $D/trace.err || { echo "$w trace failed"; tail -5 $D/trace.err; exit 1; }

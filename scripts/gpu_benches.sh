@@ -2,6 +2,7 @@
 #   BENCHES="scan highcard highcard-default inverted ssb" bash scripts/gpu_benches.sh
 # Lines land in gpurun_out/<workload>_bench.json; a summary table goes to stdout.
 set -o pipefail
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the CPU baseline and the cached-plan latencies of the summary table
 mkdir -p gpurun_out
 for w in ${BENCHES:-scan highcard inverted ssb highcard-default}; do
   timeout -k 10 ${BENCH_TIMEOUT:-420} python bench.py --workload $w --steps ${STEPS:-10} --warmup 2 ${BENCH_ARGS:-} > gpurun_out/${w}_bench.json 2> gpurun_out/${w}_bench.err || { echo "$w FAILED"; tail -20 gpurun_out/${w}_bench.err; exit 1; }
