@@ -59,7 +59,12 @@ enum pinot_amd_agg_type { PINOT_AMD_AGG_COUNT = 0, PINOT_AMD_AGG_SUM = 1, PINOT_
                           PINOT_AMD_AGG_MAX = 3, PINOT_AMD_AGG_SUMLONG = 4, PINOT_AMD_AGG_AVG = 5,
                           /* MinMaxRangeAggregationFunction: (min, max) pair built with < / > (NaN never
                            * enters it); final result max - min */
-                          PINOT_AMD_AGG_MINMAXRANGE = 6 };
+                          PINOT_AMD_AGG_MINMAXRANGE = 6,
+                          /* DistinctCountAggregationFunction: per group the set of distinct values of the
+                           * column (value identity = its id in the batch's merged dictionary: FLOAT/DOUBLE by
+                           * floatToIntBits / doubleToLongBits, one NaN, -0.0 != 0.0); final result the set's
+                           * size. See "DISTINCTCOUNT results" below. */
+                          PINOT_AMD_AGG_DISTINCTCOUNT = 7 };
 
 /* ------------------------------------------------------------------------------------------------
  * Runtime
@@ -184,14 +189,16 @@ int pinot_amd_query_add_predicate(pinot_amd_query* q, int32_t clause, const pino
  * floatToIntBits/doubleToLongBits). A raw column gets a derived dictionary twin staged on its segment
  * at the first such query (kept for later queries). */
 int pinot_amd_query_add_group_by(pinot_amd_query* q, const char* column);
-/* Aggregation function (column NULL or "*" for COUNT(*)). Returns the aggregation index via out_index. */
+/* Aggregation function (column NULL or "*" for COUNT(*)). Returns the aggregation index via out_index.
+ * PINOT_AMD_AGG_DISTINCTCOUNT takes a column of any stored type, STRING included (EINVAL for NULL / "*"). */
 int pinot_amd_query_add_aggregation(pinot_amd_query* q, int32_t agg_type, const char* column, int32_t* out_index);
 /* Aggregation over a binary arithmetic transform of two columns (SUM / MIN / MAX / AVG):
  * MultiplicationTransformFunction (times), SubtractionTransformFunction (minus),
  * AdditionTransformFunction (plus) in core/operator/transform/function/. Pinot evaluates these in
  * double; with two INT operands the device sums the exact int64 value (equal to the reference's
  * double sum while partial sums stay below 2^53), otherwise it computes in double as the
- * reference does. Needs the query-specialised (hipRTC) kernel; EUNSUPPORTED without it. */
+ * reference does. Needs the query-specialised (hipRTC) kernel; EUNSUPPORTED without it.
+ * DISTINCTCOUNT over an expression: EUNSUPPORTED. */
 enum pinot_amd_expr_op { PINOT_AMD_EXPR_COLUMN = 0, PINOT_AMD_EXPR_MUL = 1, PINOT_AMD_EXPR_SUB = 2,
                          PINOT_AMD_EXPR_ADD = 3 };
 int pinot_amd_query_add_aggregation_expr(pinot_amd_query* q, int32_t agg_type, int32_t expr_op, const char* column_a,
@@ -313,6 +320,45 @@ int pinot_amd_result_export_groups(pinot_amd_result* r, uint64_t* d_keys, uint64
                                    int32_t* h_key_words, int32_t* h_num_acc, int64_t* h_num_groups, void* stream);
 int pinot_amd_result_merge_groups(pinot_amd_result* r, const uint64_t* d_keys, const uint64_t* d_acc, int64_t n,
                                   void* stream);
+/* ------------------------------------------------------------------------------------------------
+ * DISTINCTCOUNT results (DistinctCountAggregationFunction / BaseDistinctAggregateAggregationFunction in
+ * core/query/aggregation/function/: per-group dictId bitmaps, convertToValueSet, merge = union, final = size).
+ * pinot_amd_execute of a query with at least one PINOT_AMD_AGG_DISTINCTCOUNT runs, inside the library and on the
+ * caller's stream, the base query (the query without its DISTINCTCOUNTs, or with COUNT(*) when nothing else is
+ * left) and one value-set query per distinct DISTINCTCOUNT column c: the same predicates and installed key spaces,
+ * GROUP BY g..., c, COUNT(*) only, no server table, numGroupsLimit raised to 2^30. Their groups are folded on the
+ * device into per-group value sets when the result's groups are first read. The result's groups are the base
+ * query's: with numGroupsLimit only the groups the base admitted are kept, each with all its values over the batch
+ * (Pinot would also drop, per segment, the docs of the groups that segment did not admit). DISTINCTCOUNT of a
+ * GROUP BY column is 1 per group and runs no value-set query. EUNSUPPORTED: kMaxGroupCols (16) GROUP BY columns
+ * already, and the segment-level trims (ORDER BY = GROUP BY with LIMIT >= sortAggregateLimitThreshold and no
+ * serverReturnFinalResult; minSegmentGroupTrimSize > 0 with another ORDER BY). The server table
+ * (pinot_amd_query_set_result_limit / add_order_by) may order by a DISTINCTCOUNT: its final value is the count.
+ *
+ * The result calls on such a result:
+ *   pinot_amd_execute_again            re-runs the base and the value-set queries
+ *   last_kernel_ms, algorithmic_bytes  summed over the base and the value-set queries
+ *   kernel_info                        the base's, then " +distinct(<column>:<value-set query's kernel_info>)" each
+ *   num_docs_matched, num_groups, num_groups_limit_reached, string_key, check_word: the base's
+ *   fetch                              a DISTINCTCOUNT's h_values = the count as double, h_values_i64 = the count
+ *   fetch_intermediate                 (count, 0); the set itself comes from fetch_distinct_values
+ *   accumulators, export_groups, merge_groups: EUNSUPPORTED (sets merge by union, not by accumulator op)
+ * Every read fails with EINVAL when the self-check of the base or of a value-set query failed, or when a
+ * (group, value) pair belongs to no group of a base query that could not have trimmed.
+ *
+ * DistinctCountAggregationFunction.extractGroupByResult: the value sets, CSR over the groups in fetch
+ * order (after a server table: its kept groups, in its order). h_offsets[ngroups + 1];
+ * h_values[h_offsets[g] .. h_offsets[g+1]) = group g's distinct values of aggregation agg_index, ascending
+ * merged-dictionary id, each as fetch's key encoding (int64 / double bits / index for
+ * pinot_amd_result_distinct_string). h_offsets may be NULL. h_values NULL: sizes only (h_num_values = the total).
+ * More than cap values: EOVERFLOW. EINVAL when agg_index is not a DISTINCTCOUNT of the result.
+ * --------------------------------------------------------------------------------------------- */
+int pinot_amd_result_fetch_distinct_values(pinot_amd_result* r, int32_t agg_index, int64_t cap, int64_t* h_offsets,
+                                           int64_t* h_values, int64_t* h_num_values);
+/* String value of merged-dictionary id `id` of aggregation agg_index's DISTINCTCOUNT column (NULL when it is
+ * not a STRING column or id is out of range). */
+const char* pinot_amd_result_distinct_string(pinot_amd_result* r, int32_t agg_index, int64_t id);
+
 /* The device plan: "jit" (fused scan), "jit-partitioned", "jit-hash", "jit-hash-trim"; then "-select" /
  * "-wselect" / "-fwselect" for a selection-vector plan (filter on 4-doc tiles / on 64-doc bitset words /
  * fused with the inverted-index expansion), "+admit-seq" / "+admit" for numGroupsLimit admission

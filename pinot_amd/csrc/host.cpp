@@ -72,6 +72,11 @@ hipError_t launch_export_groups(const int32_t* slots, int64_t ngroups, const uns
 hipError_t launch_merge_rows(const uint64_t* keys, const uint64_t* acc, int64_t n, int nw, int nacc_in,
                              unsigned long long* fkeys, int64_t fcap, uint64_t* facc, const DevQuery& q,
                              unsigned long long* overflow, hipStream_t st);
+hipError_t launch_distinct_fold_count(const uint64_t* ckeys, int64_t nrows, const DevKeyPack& kc, const DevKeyPack& kb,
+                                      const uint64_t* bkeys, int64_t nbase, int cbits, uint32_t* cnt, uint64_t* pair,
+                                      unsigned long long* miss, hipStream_t st);
+hipError_t launch_distinct_fold_fill(const uint64_t* sorted, int64_t nrows, int cbits, const uint32_t* cnt, int64_t nbase,
+                                     int64_t* off, int32_t* values, hipStream_t st);
 hipError_t launch_read_dict_ids(const uint8_t* packed, int bits, int64_t start, int64_t len, int32_t* out,
                                 hipStream_t st);
 hipError_t launch_pack_dict_ids(const int32_t* values, int64_t n, int bits, uint8_t* packed, hipStream_t st);
@@ -1312,7 +1317,7 @@ int pinot_amd_query_add_group_by(pinot_amd_query* q, const char* column) {
 
 int pinot_amd_query_add_aggregation(pinot_amd_query* q, int32_t agg_type, const char* column, int32_t* out_index) {
   if (!q) return fail(PINOT_AMD_EINVAL, "add_aggregation: null query");
-  if (agg_type < PINOT_AMD_AGG_COUNT || agg_type > PINOT_AMD_AGG_MINMAXRANGE)
+  if (agg_type < PINOT_AMD_AGG_COUNT || agg_type > PINOT_AMD_AGG_DISTINCTCOUNT)
     return fail(PINOT_AMD_EINVAL, "add_aggregation: bad type");
   AggSpec a{agg_type, (column && strcmp(column, "*") != 0) ? column : ""};
   if (agg_type != PINOT_AMD_AGG_COUNT && a.column.empty()) return fail(PINOT_AMD_EINVAL, "add_aggregation: column required");
@@ -1473,7 +1478,35 @@ struct Launch {
 
 enum PlanKind { PLAN_DENSE = 0, PLAN_PARTITIONED = 1, PLAN_HASH = 2, PLAN_FILTER = 3 };
 
+// DISTINCTCOUNT (execute_distinct): the result handed to the caller is the base query's result (the query without
+// its DISTINCTCOUNTs) carrying this -- one child result per distinct DISTINCTCOUNT column c (the same filter grouped
+// by (g..., c), COUNT(*) only, untrimmed) and the device buffers of the fold (distinct_fold) that turns each child's
+// (group, value) rows into per-group value sets: cnt / off (CSR over the base's groups in ascending key order) and
+// vals (merged-dictionary ids of c, ascending within a group). On destroy the children and the base go back to the
+// plan cache as the ordinary results they are; this part is dropped.
+struct DistinctFold {
+  struct Child {
+    pinot_amd_result* r = nullptr;
+    std::string column;
+    DevBuf ckeys, pair, sorted, scratch, cnt, off, vals, miss;
+    int64_t nrows = 0;  // the child's groups: (group, value) pairs
+    int cbits = 1;      // bits of c's merged id in a pair word
+    // the CSR on the host (pinot_amd_result_fetch_distinct_values), copied once per execution
+    std::vector<int64_t> h_off;
+    std::vector<int32_t> h_vals;
+    bool h_valid = false;
+  };
+  std::deque<Child> children;
+  std::vector<int32_t> base_agg_type, base_agg_acc, base_agg_acc2;  // the base's own, put back when this is dropped
+  // per aggregation of the caller's query: -1 not a DISTINCTCOUNT, k >= 0 child k, -2 - j GROUP BY column j itself
+  std::vector<int32_t> agg_child;
+  DevBuf bkeys;       // the base's groups as packed keys (key_pack layout) when its table is dense
+  int64_t nbase = 0;  // the base's groups before the server trim (the CSR's rows)
+  ~DistinctFold();
+};
+
 struct pinot_amd_result {
+  std::unique_ptr<DistinctFold> dc;  // a DISTINCTCOUNT query's result (see DistinctFold)
   hipStream_t stream = nullptr;
   PlanKind kind = PLAN_DENSE;
   DevQuery q{};                  // plan-wide: nacc, acc_op, num_keys (dense)
@@ -1613,6 +1646,35 @@ struct pinot_amd_result {
     if (ev_x) (void)hipEventDestroy(ev_x);
   }
 };
+
+DistinctFold::~DistinctFold() {
+  const bool to_pool = g_release_to_pool;  // each child's destroy sets and clears it for itself
+  for (Child& c : children) {
+    if (c.r) pinot_amd_result_destroy(c.r);
+    c.r = nullptr;
+  }
+  g_release_to_pool = to_pool;
+}
+
+// A DISTINCTCOUNT result becomes its base query's ordinary result again (before it is cached or deleted): the
+// children destroyed (each kept by the plan cache under its own identity), the base's aggregation list and its
+// (absent) server table put back.
+static void drop_distinct(pinot_amd_result* r) {
+  if (!r->dc) return;
+  r->agg_type = r->dc->base_agg_type;
+  r->agg_acc = r->dc->base_agg_acc;
+  r->agg_acc2 = r->dc->base_agg_acc2;
+  const pinot_amd_query dflt;
+  r->srv_limit = dflt.limit;
+  r->srv_order.clear();
+  r->srv_min_trim = dflt.min_trim;
+  r->srv_trim_threshold = dflt.trim_threshold;
+  r->srv_final = dflt.server_final;
+  r->srv_sort_threshold = dflt.sort_agg_threshold;
+  r->srv_safe = false;
+  r->compacted = false;
+  r->dc.reset();
+}
 
 namespace {
 
@@ -4661,8 +4723,126 @@ static int no_throw(const char* what, F&& f) {
 }
 }
 
+// A query with DISTINCTCOUNT aggregations (DistinctCountAggregationFunction: per group the set of distinct values
+// of the column; merge = union, final = size). Run as the base query -- the query without its DISTINCTCOUNTs, or
+// with COUNT(*) when nothing else is left -- plus one value-set query per distinct DISTINCTCOUNT column c: the same
+// filter and key spaces grouped by (g..., c) with c last, COUNT(*) only, no server table, numGroupsLimit raised to
+// 2^30 so that no value is cut (the base alone admits groups; Pinot would also drop, per segment, the docs of the
+// groups that segment did not admit -- its sets can be smaller for such queries). The children's groups are folded
+// into per-group value sets on the device when the result's groups are first read (distinct_fold), before the
+// server table is applied: it may order by a DISTINCTCOUNT. DISTINCTCOUNT of a GROUP BY column is 1 per group.
+static int execute_distinct(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, int32_t n, void* stream,
+                            pinot_amd_result** out) {
+  if (!segs_in || n < 1 || !out) return fail(PINOT_AMD_EINVAL, "execute: bad arguments");
+  const pinot_amd_query& U = *qq;
+  const pinot_amd_query dflt;
+  if (!U.group_by.empty() && U.limit >= 0 && !U.order_by.empty()) {
+    std::vector<bool> seen(U.group_by.size(), false);
+    bool safe = true;
+    for (const auto& ob : U.order_by) {
+      if (ob.kind != 0) safe = false;
+      else seen[ob.index] = true;
+    }
+    safe = safe && std::all_of(seen.begin(), seen.end(), [](bool b) { return b; });
+    if (safe && U.limit >= U.sort_agg_threshold && !U.server_final)
+      return fail(PINOT_AMD_EUNSUPPORTED, "DISTINCTCOUNT with a segment-level safe trim (ORDER BY = GROUP BY, LIMIT %lld "
+                                          ">= sortAggregateLimitThreshold %lld)",
+                  (long long)U.limit, (long long)U.sort_agg_threshold);
+    if (!safe && U.min_seg_trim > 0)
+      return fail(PINOT_AMD_EUNSUPPORTED, "DISTINCTCOUNT with a segment-level trim (minSegmentGroupTrimSize %lld)",
+                  (long long)U.min_seg_trim);
+  }
+  pinot_amd_query base = U;
+  base.aggs.clear();
+  base.limit = dflt.limit;
+  base.order_by.clear();
+  base.min_trim = dflt.min_trim;
+  base.trim_threshold = dflt.trim_threshold;
+  base.server_final = dflt.server_final;
+  base.sort_agg_threshold = dflt.sort_agg_threshold;
+  base.min_seg_trim = dflt.min_seg_trim;
+  auto fold = std::make_unique<DistinctFold>();
+  std::vector<int32_t> base_index(U.aggs.size(), -1);
+  std::vector<std::string> child_cols;
+  for (size_t a = 0; a < U.aggs.size(); ++a) {
+    const AggSpec& A = U.aggs[a];
+    if (A.type != PINOT_AMD_AGG_DISTINCTCOUNT) {
+      base_index[a] = (int32_t)base.aggs.size();
+      base.aggs.push_back(A);
+      fold->agg_child.push_back(-1);
+      continue;
+    }
+    auto g = std::find(U.group_by.begin(), U.group_by.end(), A.column);
+    if (g != U.group_by.end()) {  // the set of a group is its key's own value
+      fold->agg_child.push_back(-2 - (int32_t)(g - U.group_by.begin()));
+      continue;
+    }
+    auto c = std::find(child_cols.begin(), child_cols.end(), A.column);
+    if (c == child_cols.end()) {
+      child_cols.push_back(A.column);
+      c = child_cols.end() - 1;
+    }
+    fold->agg_child.push_back((int32_t)(c - child_cols.begin()));
+  }
+  if (base.aggs.empty()) base.aggs.push_back(AggSpec{PINOT_AMD_AGG_COUNT, ""});
+  if (!child_cols.empty() && U.group_by.size() >= (size_t)kMaxGroupCols)
+    return fail(PINOT_AMD_EUNSUPPORTED, "DISTINCTCOUNT with %zu GROUP BY columns (the value-set query adds one; max %d)",
+                U.group_by.size(), kMaxGroupCols);
+  pinot_amd_result* rb = nullptr;
+  if (int rc = execute_impl(&base, segs_in, n, stream, false, &rb)) return rc;
+  std::unique_ptr<pinot_amd_result, int (*)(pinot_amd_result*)> hold(rb, pinot_amd_result_destroy);
+  for (const std::string& col : child_cols) {
+    pinot_amd_query cq = base;
+    cq.group_by.push_back(col);
+    cq.aggs.assign(1, AggSpec{PINOT_AMD_AGG_COUNT, ""});
+    cq.num_groups_limit = (int64_t)1 << 30;
+    fold->children.emplace_back();
+    DistinctFold::Child& C = fold->children.back();
+    C.column = col;
+    if (int rc = execute_impl(&cq, segs_in, n, stream, false, &C.r)) return rc;  // (fold's destructor frees the others)
+  }
+  // the caller's aggregation list and server table on the base's result: a DISTINCTCOUNT's final value is word
+  // nacc + k of its group's host row (distinct_fold), or 1 for a GROUP BY column
+  fold->base_agg_type = rb->agg_type;
+  fold->base_agg_acc = rb->agg_acc;
+  fold->base_agg_acc2 = rb->agg_acc2;
+  std::vector<int32_t> t, a1, a2;
+  const int nacc = std::max(rb->q.nacc, 1);
+  for (size_t a = 0; a < U.aggs.size(); ++a) {
+    const int32_t b = base_index[a];
+    t.push_back(U.aggs[a].type);
+    a1.push_back(b >= 0 ? rb->agg_acc[b] : fold->agg_child[a] >= 0 ? nacc + fold->agg_child[a] : -1);
+    a2.push_back(b >= 0 ? rb->agg_acc2[b] : 0);
+  }
+  rb->agg_type = t;
+  rb->agg_acc = a1;
+  rb->agg_acc2 = a2;
+  rb->srv_limit = U.limit;
+  rb->srv_order = U.order_by;
+  rb->srv_min_trim = U.min_trim;
+  rb->srv_trim_threshold = U.trim_threshold;
+  rb->srv_final = U.server_final;
+  rb->srv_sort_threshold = U.sort_agg_threshold;
+  {
+    std::vector<bool> seen(U.group_by.size(), false);
+    bool only_keys = !U.order_by.empty();
+    for (const auto& ob : U.order_by) {
+      if (ob.kind != 0) only_keys = false;
+      else seen[ob.index] = true;
+    }
+    rb->srv_safe = only_keys && std::all_of(seen.begin(), seen.end(), [](bool b) { return b; });
+  }
+  rb->compacted = false;
+  rb->dc = std::move(fold);
+  *out = hold.release();
+  return 0;
+}
+
 int pinot_amd_execute(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, int32_t n, void* stream,
                       pinot_amd_result** out) {
+  if (qq && std::any_of(qq->aggs.begin(), qq->aggs.end(),
+                        [](const AggSpec& a) { return a.type == PINOT_AMD_AGG_DISTINCTCOUNT; }))
+    return no_throw("execute", [&] { return execute_distinct(qq, segs_in, n, stream, out); });
   return no_throw("execute", [&] { return execute_impl(qq, segs_in, n, stream, false, out); });
 }
 
@@ -4686,7 +4866,13 @@ int pinot_amd_result_bitset(pinot_amd_result* r, int32_t segment_index, const ui
 int pinot_amd_execute_again(pinot_amd_result* r, void* stream) {
   if (!r) return fail(PINOT_AMD_EINVAL, "execute_again: null result");
   r->stream = (hipStream_t)stream;
-  return run_plan(r);
+  if (int rc = run_plan(r)) return rc;
+  if (r->dc)  // a DISTINCTCOUNT result: its value-set queries too, on the same stream
+    for (DistinctFold::Child& c : r->dc->children) {
+      c.r->stream = (hipStream_t)stream;
+      if (int rc = run_plan(c.r)) return rc;
+    }
+  return 0;
 }
 
 int pinot_amd_result_destroy(pinot_amd_result* r) {
@@ -4694,6 +4880,11 @@ int pinot_amd_result_destroy(pinot_amd_result* r) {
   // the result's work is finished before its blocks go to the device pool (a caller still reading a
   // pinot_amd_result_bitset buffer on another stream must order that read before this call)
   const bool idle = hipStreamSynchronize(r->stream) == hipSuccess;
+  if (r->dc) {  // the children first (each to the plan cache or freed), then the base as the ordinary result it is
+    g_release_to_pool = idle;
+    drop_distinct(r);
+    g_release_to_pool = false;
+  }
   if (idle && plan_cache_put(r)) return 0;  // kept for the next execute of its identity
   g_release_to_pool = idle;
   delete r;
@@ -4865,11 +5056,23 @@ static int verify_partitioned(pinot_amd_result* r, const std::vector<unsigned lo
   return fail(PINOT_AMD_EINVAL, "%s", r->check_msg.c_str());
 }
 
+// a DISTINCTCOUNT result is void when the self-check of any of its value-set queries failed
+static int verify_children(pinot_amd_result* r) {
+  if (!r->dc) return 0;
+  for (DistinctFold::Child& ch : r->dc->children) {
+    std::vector<unsigned long long> c;
+    if (int rc = read_counters(ch.r, &c)) return rc;
+    if (int rc = verify_partitioned(ch.r, c)) return rc;
+  }
+  return 0;
+}
+
 int pinot_amd_result_num_docs_matched(pinot_amd_result* r, int64_t* h_out) {
   if (!r || !h_out) return fail(PINOT_AMD_EINVAL, "num_docs_matched: bad arguments");
   std::vector<unsigned long long> c;
   if (int rc = read_counters(r, &c)) return rc;
   if (int rc = verify_partitioned(r, c)) return rc;
+  if (int rc = verify_children(r)) return rc;
   // per launch: the scan / count pass and the direct-atomic scan both count every matching doc;
   // whichever ran has the total (partitioned plans run one of them)
   int64_t total = 0;
@@ -4902,13 +5105,18 @@ int pinot_amd_result_algorithmic_bytes(pinot_amd_result* r, double* h_bytes) {
       b += L.col_bytes * m / (double)L.docs;
     }
   }
+  if (r->dc)  // a DISTINCTCOUNT result: the value-set queries' bytes too
+    for (DistinctFold::Child& ch : r->dc->children) {
+      double cb = 0;
+      if (int rc = pinot_amd_result_algorithmic_bytes(ch.r, &cb)) return rc;
+      b += cb;
+    }
   *h_bytes = b;
   return 0;
 }
 
-const char* pinot_amd_result_kernel_info(pinot_amd_result* r) {
-  if (!r) return "";
-  static thread_local std::string info;
+static std::string kernel_info_of(pinot_amd_result* r) {
+  std::string info;
   switch (r->kind) {
     case PLAN_PARTITIONED: info = "jit-partitioned"; break;
     case PLAN_HASH: info = r->trim ? "jit-hash-trim" : "jit-hash"; break;
@@ -4930,6 +5138,15 @@ const char* pinot_amd_result_kernel_info(pinot_amd_result* r) {
     info += seq ? "+admit-seq" : "+admit";
   }
   if (r->launches.size() > 1) info += " x" + std::to_string(r->launches.size());
+  if (r->dc)  // the plan that served each DISTINCTCOUNT column's value sets
+    for (DistinctFold::Child& ch : r->dc->children) info += " +distinct(" + ch.column + ":" + kernel_info_of(ch.r) + ")";
+  return info;
+}
+
+const char* pinot_amd_result_kernel_info(pinot_amd_result* r) {
+  if (!r) return "";
+  static thread_local std::string info;
+  info = kernel_info_of(r);
   return info.c_str();
 }
 
@@ -4939,6 +5156,12 @@ int pinot_amd_result_last_kernel_ms(pinot_amd_result* r, double* h_ms) {
   float ms = 0;
   HIP_OK(hipEventElapsedTime(&ms, r->ev0, r->ev1));
   *h_ms = ms;
+  if (r->dc)  // a DISTINCTCOUNT result: the value-set queries' scans too
+    for (DistinctFold::Child& ch : r->dc->children) {
+      double cm = 0;
+      if (int rc = pinot_amd_result_last_kernel_ms(ch.r, &cm)) return rc;
+      *h_ms += cm;
+    }
   return 0;
 }
 
@@ -5026,8 +5249,18 @@ static int compact_slots(pinot_amd_result* r, const GroupTable& T, hipStream_t s
 }
 
 static int server_trim(pinot_amd_result* r);
+static int distinct_fold(pinot_amd_result* r, const uint64_t* d_hash_keys, int64_t ng);
+
+// words of a group's host row (cacc): its accumulators; a DISTINCTCOUNT result appends each value-set query's
+// distinct count and the group's index before the server table reorders the rows (the CSR's row)
+static int cacc_stride(const pinot_amd_result* r) {
+  return std::max(r->q.nacc, 1) + (r->dc ? (int)r->dc->children.size() + 1 : 0);
+}
 
 static int compact_groups(pinot_amd_result* r) {
+  if (r->dc && r->dc->children.size())  // a failed self-check of a value-set query voids every read
+    for (DistinctFold::Child& ch : r->dc->children)
+      if (ch.r->check_failed) return fail(PINOT_AMD_EINVAL, "%s", ch.r->check_msg.c_str());
   if (r->compacted) return 0;
   hipStream_t st = r->stream;
   const int nacc = std::max(r->q.nacc, 1);
@@ -5040,6 +5273,8 @@ static int compact_groups(pinot_amd_result* r) {
       HIP_OK(hipMemcpyAsync(r->cacc.data(), r->acc.p, (size_t)nacc * 8, hipMemcpyDeviceToHost, st));
       HIP_OK(hipStreamSynchronize(st));
     }
+    if (r->dc)
+      if (int rc = distinct_fold(r, nullptr, 1)) return rc;
     r->compacted = true;
     return 0;
   }
@@ -5052,6 +5287,7 @@ static int compact_groups(pinot_amd_result* r) {
   r->ngroups = ng;
   r->ckeys.resize((size_t)ng * nwk);
   r->cacc.resize((size_t)ng * nacc);
+  const uint64_t* d_sorted_keys = nullptr;  // hash tables: the groups' key words in ascending key order, on the device
   if (ng > 0) {
     if (int rc = okeys.ensure((size_t)ng * nwk * 8)) return rc;
     if (int rc = oacc.ensure((size_t)ng * nacc * 8)) return rc;
@@ -5078,7 +5314,10 @@ static int compact_groups(pinot_amd_result* r) {
     HIP_OK(hipMemcpyAsync(r->ckeys.data(), src_keys, r->ckeys.size() * 8, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(r->cacc.data(), src_acc, r->cacc.size() * 8, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
+    if (hash) d_sorted_keys = (const uint64_t*)src_keys;
   }
+  if (r->dc)  // the value sets, and their sizes into the groups' rows, before the server table orders by them
+    if (int rc = distinct_fold(r, d_sorted_keys, ng)) return rc;
   if (int rc = server_trim(r)) return rc;
   r->compacted = true;
   return 0;
@@ -5093,6 +5332,7 @@ int pinot_amd_result_num_groups_limit_reached(pinot_amd_result* r, int32_t* h_ou
   std::vector<unsigned long long> c;
   if (int rc = read_counters(r, &c)) return rc;
   if (int rc = verify_partitioned(r, c)) return rc;  // a void execution reports no flag either
+  if (int rc = verify_children(r)) return rc;
   *h_out = c[3 * r->launches.size()] != 0 ? 1 : 0;
   return 0;
 }
@@ -5120,6 +5360,12 @@ static double decode_ordered(uint64_t u, int op) {
 // final value of aggregation a from a group's accumulator words A (AggregationFunction.extractFinalResult):
 // *v as double, *vi the exact int64 for COUNT / SUMLONG / integer SUM within int64
 static void final_value(const pinot_amd_result* r, const uint64_t* A, int a, double* v_out, int64_t* vi_out) {
+  if (r->agg_type[a] == PINOT_AMD_AGG_DISTINCTCOUNT) {
+    // the set's size: the fold's count in the group's row, or 1 for a GROUP BY column (its key's own value)
+    *vi_out = r->agg_acc[a] < 0 ? 1 : (int64_t)A[r->agg_acc[a]];
+    *v_out = (double)*vi_out;
+    return;
+  }
   const int acc = r->agg_acc[a];
   const int op = r->q.acc_op[acc];
   const uint64_t w = A[acc];
@@ -5193,7 +5439,7 @@ static int java_double_compare(double a, double b) {
 static int server_trim(pinot_amd_result* r) {
   r->srv_trimmed = false;
   if (r->srv_limit < 0 || r->num_group_by == 0) return 0;
-  const int nacc = std::max(r->q.nacc, 1);
+  const int nacc = cacc_stride(r);  // words of a group's host row
   const bool hash = r->kind == PLAN_HASH || r->merged;
   const int nwk = r->merged ? r->mnw : hash ? r->nw : 1;
   int64_t keep;
@@ -5266,7 +5512,7 @@ int pinot_amd_result_fetch(pinot_amd_result* r, int64_t cap, int64_t* h_keys, do
   if (!r || cap < 0 || !h_num_fetched) return fail(PINOT_AMD_EINVAL, "fetch: bad arguments");
   if (int rc = no_throw("fetch", [&] { return compact_groups(r); })) return rc;
   const int na = (int)r->agg_type.size();
-  const int nacc = std::max(r->q.nacc, 1);
+  const int nacc = cacc_stride(r);
   const bool hash = r->kind == PLAN_HASH || r->merged;
   const int nwk = r->merged ? r->mnw : hash ? r->nw : 1;
   if (r->ngroups > cap) return fail(PINOT_AMD_EOVERFLOW, "fetch: %lld groups exceed capacity %lld", (long long)r->ngroups,
@@ -5323,7 +5569,7 @@ int pinot_amd_result_fetch_intermediate(pinot_amd_result* r, int64_t cap, double
     return fail(PINOT_AMD_EOVERFLOW, "fetch_intermediate: %lld groups exceed capacity %lld", (long long)r->ngroups,
                 (long long)cap);
   const int na = (int)r->agg_type.size();
-  const int nacc = std::max(r->q.nacc, 1);
+  const int nacc = cacc_stride(r);
   std::vector<double> v((size_t)r->ngroups * na);
   std::vector<int64_t> vi((size_t)r->ngroups * na);
   int64_t got = 0;
@@ -5373,6 +5619,7 @@ int64_t pinot_amd_selfcheck_failures(void) { return (int64_t)g_selfcheck_failure
 int pinot_amd_result_accumulators(pinot_amd_result* r, int32_t* h_num_slots, int64_t* h_num_key_slots,
                                   void** h_slot_ptrs, int32_t* h_slot_ops) {
   if (!r || !h_num_slots || !h_num_key_slots) return fail(PINOT_AMD_EINVAL, "accumulators: bad arguments");
+  if (r->dc) return fail(PINOT_AMD_EUNSUPPORTED, "accumulators: a DISTINCTCOUNT result's value sets merge by union");
   if (r->kind == PLAN_HASH || r->merged)
     return fail(PINOT_AMD_EUNSUPPORTED, "accumulators: hash-table (and merged) results merge by value "
                                         "(pinot_amd_result_export_groups / pinot_amd_result_merge_groups)");
@@ -5439,6 +5686,7 @@ int pinot_amd_result_export_groups(pinot_amd_result* r, uint64_t* d_keys, uint64
                                    int32_t* h_key_words, int32_t* h_num_acc, int64_t* h_num_groups, void* stream) {
   if (!r || !h_key_words || !h_num_acc || !h_num_groups || cap < 0)
     return fail(PINOT_AMD_EINVAL, "export_groups: bad arguments");
+  if (r->dc) return fail(PINOT_AMD_EUNSUPPORTED, "export_groups: a DISTINCTCOUNT result's value sets merge by union");
   return no_throw("export_groups", [&]() -> int {
     if (r->num_group_by == 0 || r->q.nacc == 0)
       return fail(PINOT_AMD_EUNSUPPORTED, "export_groups: not a GROUP BY result with aggregations");
@@ -5471,6 +5719,7 @@ int pinot_amd_result_export_groups(pinot_amd_result* r, uint64_t* d_keys, uint64
 int pinot_amd_result_merge_groups(pinot_amd_result* r, const uint64_t* d_keys, const uint64_t* d_acc, int64_t n,
                                   void* stream) {
   if (!r || n < 0 || (n > 0 && (!d_keys || !d_acc))) return fail(PINOT_AMD_EINVAL, "merge_groups: bad arguments");
+  if (r->dc) return fail(PINOT_AMD_EUNSUPPORTED, "merge_groups: a DISTINCTCOUNT result's value sets merge by union");
   return no_throw("merge_groups", [&]() -> int {
     if (r->num_group_by == 0 || r->q.nacc == 0)
       return fail(PINOT_AMD_EUNSUPPORTED, "merge_groups: not a GROUP BY result with aggregations");
@@ -5509,3 +5758,178 @@ int pinot_amd_result_merge_groups(pinot_amd_result* r, const uint64_t* d_keys, c
 }
 
 const char* pinot_amd_result_plan_timing(pinot_amd_result* r) { return r ? r->plan_timing.c_str() : ""; }
+
+// ------------------------------------------------------------------------------------------------
+// DISTINCTCOUNT: the fold of the value-set queries' groups into per-group value sets, on the device
+// ------------------------------------------------------------------------------------------------
+extern "C" {
+
+// Called by compact_groups on a DISTINCTCOUNT result once the base's ng groups are compacted in ascending key
+// order (d_hash_keys: their packed key words on the device when the base's table is a hash table) and before the
+// server table. Both sides go through the export layout (key_pack): the base may be dense where a child is a hash
+// table, with other packings and word counts. Per child: its groups exported as packed (g..., c) keys; the count
+// kernel finds each row's base group and emits (group, value) pair words; the pairs sorted (sort_rows_by_key) put
+// each group's values together, ascending, so two executions return the same bytes; the scan of the counts gives
+// the CSR offsets. Only the counts cross PCIe here (appended to the groups' host rows, with each group's index:
+// cacc_stride); the CSR stays in the result's device buffers until pinot_amd_result_fetch_distinct_values.
+// Without GROUP BY the one group's key is the empty key: every child row is its value.
+static int distinct_fold(pinot_amd_result* r, const uint64_t* d_hash_keys, int64_t ng) {
+  DistinctFold& D = *r->dc;
+  hipStream_t st = r->stream;
+  const int nacc = std::max(r->q.nacc, 1);
+  const int nch = (int)D.children.size();
+  const int S = cacc_stride(r);
+  if (ng >= ((int64_t)1 << 31)) return fail(PINOT_AMD_EUNSUPPORTED, "DISTINCTCOUNT over %lld groups", (long long)ng);
+  D.nbase = ng;
+  DevKeyPack kb;
+  memset(&kb, 0, sizeof(kb));
+  const uint64_t* bkeys = nullptr;
+  if (nch && ng > 0) {
+    if (r->num_group_by == 0) {  // the empty key: one zero word
+      kb.nw = 1;
+      if (int rc = D.bkeys.ensure(8)) return rc;
+      HIP_OK(hipMemsetAsync(D.bkeys.p, 0, 8, st));
+      bkeys = (const uint64_t*)D.bkeys.p;
+    } else {
+      if (int rc = key_pack(r, &kb)) return rc;
+      if (d_hash_keys) {
+        if (kb.nw != r->nw) return fail(PINOT_AMD_EINVAL, "DISTINCTCOUNT: key packing mismatch");
+        bkeys = d_hash_keys;
+      } else {
+        const GroupTable T = group_table(r);
+        if (int rc = D.bkeys.ensure((size_t)ng * kb.nw * 8)) return rc;
+        HIP_OK(launch_export_groups((const int32_t*)r->c_idx.p, ng, nullptr, T.slots, T.acc, 0, kb, (uint64_t*)D.bkeys.p,
+                                    nullptr, st));
+        bkeys = (const uint64_t*)D.bkeys.p;
+      }
+    }
+  }
+  std::vector<std::vector<uint32_t>> hcnt((size_t)nch);
+  std::vector<unsigned long long> hmiss((size_t)nch, 0);
+  for (int k = 0; k < nch; ++k) {
+    DistinctFold::Child& C = D.children[(size_t)k];
+    pinot_amd_result* c = C.r;
+    C.h_valid = false;
+    if (int rc = check_overflow(c)) return rc;  // (the child's self-check too)
+    const GroupTable T = group_table(c);
+    int64_t nrows = 0;
+    if (int rc = compact_slots(c, T, st, &nrows)) return rc;
+    if (nrows >= ((int64_t)1 << 31))
+      return fail(PINOT_AMD_EUNSUPPORTED, "DISTINCTCOUNT(%s): %lld (group, value) pairs", C.column.c_str(), (long long)nrows);
+    C.nrows = nrows;
+    DevKeyPack kc;
+    if (int rc = key_pack(c, &kc)) return rc;
+    if (kc.ncols != r->num_group_by + 1 || (c->kind == PLAN_HASH && kc.nw != c->nw))
+      return fail(PINOT_AMD_EINVAL, "DISTINCTCOUNT(%s): key packing mismatch", C.column.c_str());
+    C.cbits = bits_for(kc.size[kc.ncols - 1]);
+    if (int rc = C.cnt.ensure((size_t)(ng + 1) * 4)) return rc;
+    if (int rc = C.off.ensure((size_t)(ng + 1) * 8)) return rc;
+    if (int rc = C.miss.ensure(8)) return rc;
+    if (nrows > 0) {
+      if (int rc = C.ckeys.ensure((size_t)nrows * kc.nw * 8)) return rc;
+      if (int rc = C.pair.ensure((size_t)nrows * 8)) return rc;
+      if (int rc = C.sorted.ensure((size_t)nrows * 8)) return rc;
+      if (int rc = C.scratch.ensure(sort_rows_scratch(nrows))) return rc;
+      if (int rc = C.vals.ensure((size_t)nrows * 4)) return rc;
+      HIP_OK(launch_export_groups((const int32_t*)c->c_idx.p, nrows, T.keys, T.slots, T.acc, 0, kc, (uint64_t*)C.ckeys.p,
+                                  nullptr, st));
+    }
+    HIP_OK(launch_distinct_fold_count((const uint64_t*)C.ckeys.p, nrows, kc, kb, bkeys, ng, C.cbits, (uint32_t*)C.cnt.p,
+                                      (uint64_t*)C.pair.p, (unsigned long long*)C.miss.p, st));
+    const int pair_bits = C.cbits + bits_for(ng + 1);  // group indices 0 .. ng (ng: no base group)
+    HIP_OK(sort_rows_by_key((const uint64_t*)C.pair.p, 1, &pair_bits, nullptr, 0, nrows, C.scratch.p, (uint64_t*)C.sorted.p,
+                            nullptr, st));
+    HIP_OK(launch_distinct_fold_fill((const uint64_t*)C.sorted.p, nrows, C.cbits, (const uint32_t*)C.cnt.p, ng,
+                                     (int64_t*)C.off.p, (int32_t*)C.vals.p, st));
+    hcnt[(size_t)k].assign((size_t)ng, 0);
+    if (ng > 0) HIP_OK(hipMemcpyAsync(hcnt[(size_t)k].data(), C.cnt.p, (size_t)ng * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(&hmiss[(size_t)k], C.miss.p, 8, hipMemcpyDeviceToHost, st));
+  }
+  HIP_OK(hipStreamSynchronize(st));
+  // a child row without a base group: a group the base did not admit under numGroupsLimit (its values are dropped
+  // with it); otherwise the two queries disagree about the groups, and the result is void
+  for (int k = 0; k < nch; ++k)
+    if (hmiss[(size_t)k] != 0 && !r->limit_possible)
+      return fail(PINOT_AMD_EINVAL, "DISTINCTCOUNT(%s): %llu (group, value) pairs belong to no group of the query; the result "
+                                    "is void", D.children[(size_t)k].column.c_str(), hmiss[(size_t)k]);
+  std::vector<uint64_t> rows((size_t)ng * S);
+  for (int64_t g = 0; g < ng; ++g) {
+    std::copy_n(&r->cacc[(size_t)g * nacc], nacc, &rows[(size_t)g * S]);
+    for (int k = 0; k < nch; ++k) rows[(size_t)g * S + nacc + k] = hcnt[(size_t)k][(size_t)g];
+    rows[(size_t)g * S + S - 1] = (uint64_t)g;
+  }
+  r->cacc.swap(rows);
+  return 0;
+}
+
+}  // extern "C"
+
+// the merged dictionary of aggregation agg_index's DISTINCTCOUNT column, or null
+static const MergedKeyColumn* distinct_dictionary(pinot_amd_result* r, int32_t agg_index) {
+  if (!r || !r->dc || agg_index < 0 || agg_index >= (int32_t)r->dc->agg_child.size()) return nullptr;
+  const int32_t k = r->dc->agg_child[(size_t)agg_index];
+  if (k == -1) return nullptr;
+  if (k >= 0) return r->dc->children[(size_t)k].r->keys.back().get();
+  return r->keys[(size_t)(-2 - k)].get();
+}
+
+int pinot_amd_result_fetch_distinct_values(pinot_amd_result* r, int32_t agg_index, int64_t cap, int64_t* h_offsets,
+                                           int64_t* h_values, int64_t* h_num_values) {
+  if (!r || cap < 0 || !h_num_values) return fail(PINOT_AMD_EINVAL, "fetch_distinct_values: bad arguments");
+  const MergedKeyColumn* m = distinct_dictionary(r, agg_index);
+  if (!m) return fail(PINOT_AMD_EINVAL, "fetch_distinct_values: aggregation %d is not a DISTINCTCOUNT of this result", agg_index);
+  return no_throw("fetch_distinct_values", [&]() -> int {
+    if (int rc = compact_groups(r)) return rc;
+    DistinctFold& D = *r->dc;
+    const int32_t k = D.agg_child[(size_t)agg_index];
+    const int S = cacc_stride(r);
+    const int64_t ng = r->ngroups;
+    auto encode = [&](int64_t id) -> int64_t {
+      int64_t o;
+      if (m->type == T_STRING) o = id;
+      else if (is_float(m->type)) memcpy(&o, &m->vd[(size_t)id], 8);
+      else o = m->vi[(size_t)id];
+      return o;
+    };
+    int64_t total = 0;
+    for (int64_t g = 0; g < ng; ++g) {
+      if (h_offsets) h_offsets[g] = total;
+      total += k >= 0 ? (int64_t)r->cacc[(size_t)g * S + (S - 1 - (int)D.children.size()) + k] : 1;
+    }
+    if (h_offsets) h_offsets[ng] = total;
+    *h_num_values = total;
+    if (!h_values) return 0;  // sizing call
+    if (total > cap)
+      return fail(PINOT_AMD_EOVERFLOW, "fetch_distinct_values: %lld values exceed capacity %lld", (long long)total, (long long)cap);
+    if (k < 0) {  // a GROUP BY column: each group's set is its key's value
+      for (int64_t g = 0; g < ng; ++g) h_values[g] = encode(group_key_id(r, g, -2 - k));
+      return 0;
+    }
+    DistinctFold::Child& C = D.children[(size_t)k];
+    if (!C.h_valid) {  // the CSR over the groups before the server table, once per execution
+      C.h_off.assign((size_t)D.nbase + 1, 0);
+      HIP_OK(hipMemcpyAsync(C.h_off.data(), C.off.p, C.h_off.size() * 8, hipMemcpyDeviceToHost, r->stream));
+      HIP_OK(hipStreamSynchronize(r->stream));
+      const int64_t nv = C.h_off.back();
+      if (nv < 0 || nv > C.nrows) return fail(PINOT_AMD_EINVAL, "fetch_distinct_values: inconsistent value sets");
+      C.h_vals.assign((size_t)nv, 0);
+      if (nv > 0) {
+        HIP_OK(hipMemcpyAsync(C.h_vals.data(), C.vals.p, (size_t)nv * 4, hipMemcpyDeviceToHost, r->stream));
+        HIP_OK(hipStreamSynchronize(r->stream));
+      }
+      C.h_valid = true;
+    }
+    int64_t o = 0;
+    for (int64_t g = 0; g < ng; ++g) {  // the rows the server table kept, in its order
+      const int64_t src = (int64_t)r->cacc[(size_t)g * S + S - 1];
+      for (int64_t i = C.h_off[(size_t)src]; i < C.h_off[(size_t)src + 1]; ++i) h_values[o++] = encode(C.h_vals[(size_t)i]);
+    }
+    return 0;
+  });
+}
+
+const char* pinot_amd_result_distinct_string(pinot_amd_result* r, int32_t agg_index, int64_t id) {
+  const MergedKeyColumn* m = distinct_dictionary(r, agg_index);
+  if (!m || m->type != T_STRING || id < 0 || id >= (int64_t)m->vs.size()) return nullptr;
+  return m->vs[(size_t)id].c_str();
+}

@@ -889,6 +889,64 @@ __global__ void export_groups_kernel(const int32_t* slots, int64_t ngroups, cons
   }
 }
 
+// DISTINCTCOUNT fold (DistinctCountAggregationFunction's per-group dictId sets, built from two results): the
+// child result's groups are (g..., c) rows, the base result's groups are the query's. Per child row: the column
+// ids decoded with the child's packing, the g prefix packed again as the base packs it, and the base group b
+// found by binary search over the base's packed keys (ascending, compared word nw - 1 first). cnt[b] counts
+// the row (its c is one distinct value of b); pair[i] = b << cbits | c id orders the rows by (group, value).
+// A row without a base group gets b = nbase (it sorts behind every group) and is counted in *miss.
+__global__ void __launch_bounds__(kBlock) distinct_fold_count_kernel(const uint64_t* __restrict__ ckeys, int64_t nrows,
+                                                                     DevKeyPack kc, DevKeyPack kb,
+                                                                     const uint64_t* __restrict__ bkeys, int64_t nbase,
+                                                                     int cbits, uint32_t* cnt, uint64_t* __restrict__ pair,
+                                                                     unsigned long long* miss) {
+  const int last = kc.ncols - 1;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nrows; i += (int64_t)gridDim.x * blockDim.x) {
+    uint64_t kw[kMaxKeyWords];
+    for (int w = 0; w < kb.nw; ++w) kw[w] = 0ull;
+    uint64_t cid = 0;
+    for (int j = 0; j <= last; ++j) {
+      const int b = 64 - __clzll((unsigned long long)(kc.size[j] - 1) | 1ull);  // bits_for(size): the field's width
+      const uint64_t id = (ckeys[i * kc.nw + kc.word[j]] >> kc.shift[j]) & (b >= 64 ? ~0ull : (1ull << b) - 1ull);
+      if (j == last) cid = id;
+      else kw[kb.word[j]] |= id << kb.shift[j];
+    }
+    int64_t lo = 0, hi = nbase;  // first base row >= kw
+    while (lo < hi) {
+      const int64_t mid = lo + ((hi - lo) >> 1);
+      int c = 0;
+      for (int w = kb.nw - 1; w >= 0 && c == 0; --w) {
+        const uint64_t x = bkeys[mid * kb.nw + w];
+        c = x < kw[w] ? -1 : x > kw[w] ? 1 : 0;
+      }
+      if (c < 0) lo = mid + 1;
+      else hi = mid;
+    }
+    bool found = lo < nbase;
+    for (int w = 0; w < kb.nw && found; ++w) found = bkeys[lo * kb.nw + w] == kw[w];
+    if (found) {
+      atomicAdd(cnt + lo, 1u);  // result unused: a non-returning atomic
+    } else {
+      lo = nbase;
+      atomicAdd(miss, 1ull);
+    }
+    pair[i] = ((uint64_t)lo << cbits) | cid;
+  }
+}
+
+// The pairs sorted by (group, value): row i of group b sits at off[b] + (its rank among b's values) = i, since
+// the groups' rows follow each other in group order and rows without a group come last. Writes the value id
+// into its group's range [off[b], off[b + 1]) of `values` (nrows entries) -- ascending within the group; off is
+// the exclusive scan of cnt, so that range is where the sort left the group's rows.
+__global__ void __launch_bounds__(kBlock) distinct_fold_fill_kernel(const uint64_t* __restrict__ sorted, int64_t nrows,
+                                                                    int cbits, int64_t nbase,
+                                                                    int32_t* __restrict__ values) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nrows; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t p = sorted[i];
+    if ((int64_t)(p >> cbits) < nbase) values[i] = (int32_t)(p & ((1ull << cbits) - 1ull));
+  }
+}
+
 __global__ void merge_rows_kernel(const uint64_t* keys, const uint64_t* acc, int64_t n, int nw, int nacc_in,
                                   unsigned long long* fkeys, int64_t fcap, uint64_t* facc, DevQuery q,
                                   unsigned long long* overflow) {
@@ -2086,6 +2144,30 @@ hipError_t launch_merge_rows(const uint64_t* keys, const uint64_t* acc, int64_t 
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(merge_rows_kernel, dim3(grid_cap(n, kBlock, 8192)), dim3(kBlock), 0, st, keys, acc, n, nw, nacc_in,
                      fkeys, fcap, facc, q, overflow);
+  return hipGetLastError();
+}
+
+// DISTINCTCOUNT fold, first half: cnt (nbase + 1 words, zeroed here) counts each base group's child rows, pair
+// gets the rows' (group, value) words, *miss the rows without a base group.
+hipError_t launch_distinct_fold_count(const uint64_t* ckeys, int64_t nrows, const DevKeyPack& kc, const DevKeyPack& kb,
+                                      const uint64_t* bkeys, int64_t nbase, int cbits, uint32_t* cnt, uint64_t* pair,
+                                      unsigned long long* miss, hipStream_t st) {
+  hipError_t e = hipMemsetAsync(cnt, 0, (size_t)(nbase + 1) * 4, st);
+  if (e == hipSuccess) e = hipMemsetAsync(miss, 0, 8, st);
+  if (e != hipSuccess || nrows <= 0) return e;
+  hipLaunchKernelGGL(distinct_fold_count_kernel, dim3(grid_cap(nrows, kBlock, 8192)), dim3(kBlock), 0, st, ckeys, nrows, kc,
+                     kb, bkeys, nbase, cbits, cnt, pair, miss);
+  return hipGetLastError();
+}
+
+// second half, over the pairs sorted by (group, value): off[0 .. nbase] = the exclusive scan of cnt (the row scan
+// of the partitioned plan's histograms, one row) and the value ids written in that order
+hipError_t launch_distinct_fold_fill(const uint64_t* sorted, int64_t nrows, int cbits, const uint32_t* cnt, int64_t nbase,
+                                     int64_t* off, int32_t* values, hipStream_t st) {
+  hipLaunchKernelGGL(partition_row_scan_kernel, dim3(1), dim3(kBlock), 0, st, cnt, nbase, off, off + nbase);
+  if (nrows > 0)
+    hipLaunchKernelGGL(distinct_fold_fill_kernel, dim3(grid_cap(nrows, kBlock, 8192)), dim3(kBlock), 0, st, sorted, nrows,
+                       cbits, nbase, values);
   return hipGetLastError();
 }
 

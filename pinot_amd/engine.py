@@ -25,14 +25,15 @@ import numpy as np
 
 from . import _lib
 from ._lib import ColumnSpec, PredicateSpec, check, lib
-from .query import (JavaDouble, QueryContext, fold_distinct_count, parse_sql, reduce_rows, server_table,
-                    split_distinct_count)
+from .query import (DistinctSize, JavaDouble, QueryContext, fold_distinct_count, parse_sql, reduce_rows,
+                    server_table, sets_from_csr, split_distinct_count)
 from .segment import ColumnBuffers, SegmentBuffers, DOUBLE, FLOAT, INT, LONG, STRING
 
 TYPE_CODE = {INT: 0, LONG: 1, FLOAT: 2, DOUBLE: 3, STRING: 4}
 ENC_CODE = {"FIXED_BIT": 0, "RAW": 1, "SORTED": 2}
 PRED_CODE = {"EQ": 0, "NOT_EQ": 1, "IN": 2, "NOT_IN": 3, "RANGE": 4}
-AGG_CODE = {"COUNT": 0, "SUM": 1, "MIN": 2, "MAX": 3, "SUMLONG": 4, "AVG": 5, "MINMAXRANGE": 6}
+AGG_CODE = {"COUNT": 0, "SUM": 1, "MIN": 2, "MAX": 3, "SUMLONG": 4, "AVG": 5, "MINMAXRANGE": 6,
+            "DISTINCTCOUNT": 7}
 EXPR_CODE = {"MUL": 1, "SUB": 2, "ADD": 3}
 
 
@@ -232,7 +233,9 @@ class QueryResult:
     def __init__(self, handle, qc: QueryContext, agg_slots: List[tuple], key_types: List[str]):
         self._h = handle
         self.qc = qc
-        self._agg_slots = agg_slots      # per qc aggregation: ('direct', native_idx) | ('avg', sum_idx)
+        # per qc aggregation: ('direct', native_idx) | ('avg', sum_idx, count_idx) | ('range', native_idx) |
+        # ('distinct', native_idx, stored type of the column): DISTINCTCOUNT executed by the library
+        self._agg_slots = agg_slots
         self._key_types = key_types
         self._merged_reached = None      # numGroupsLimitReached OR-ed over ranks by dist.merge_result
 
@@ -362,10 +365,31 @@ class QueryResult:
                                                         C.byref(got2)), "fetch_intermediate")
         return got, keys, vals, vals_i, pairs
 
-    def groups(self, arrays=None) -> Dict[tuple, list]:
+    def distinct_sets(self, native_idx: int, stored_type: str, num_groups: int) -> List[frozenset]:
+        """The value sets of library aggregation `native_idx` (a DISTINCTCOUNT), one frozenset per group in fetch
+        order (pinot_amd_result_fetch_distinct_values -> query.sets_from_csr)."""
+        L = lib()
+        total = C.c_int64()
+        check(L.pinot_amd_result_fetch_distinct_values(self._h, native_idx, 0, None, None, C.byref(total)),
+              "fetch_distinct_values")
+        off = np.zeros(num_groups + 1, dtype=np.int64)
+        vals = np.zeros(max(total.value, 1), dtype=np.int64)
+        check(L.pinot_amd_result_fetch_distinct_values(self._h, native_idx, total.value,
+                                                       off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                       vals.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(total)),
+              "fetch_distinct_values")
+        vals = vals[:total.value]
+        strings = None
+        if stored_type == STRING:
+            strings = {int(i): L.pinot_amd_result_distinct_string(self._h, native_idx, int(i)).decode()
+                       for i in np.unique(vals)}
+        return sets_from_csr(off, vals, stored_type, strings)
+
+    def groups(self, arrays=None, distinct_sizes: bool = False) -> Dict[tuple, list]:
         """key tuple (group-by values; () for aggregation-only) -> intermediate result per aggregation.
         Converted column-wise (numpy -> Python lists, zipped), not group by group. `arrays`: the output of
-        an earlier fetch_arrays() of this execution (not fetched again)."""
+        an earlier fetch_arrays() of this execution (not fetched again). distinct_sizes: a library-executed
+        DISTINCTCOUNT's partial is only its size (query.DistinctSize, from the fetch) instead of the value set."""
         L = lib()
         got, keys, vals, vals_i, pairs = self.fetch_arrays() if arrays is None else arrays
         n = got.value
@@ -393,6 +417,11 @@ class QueryResult:
         for a, slot in zip(self.qc.aggregations, self._agg_slots):
             if slot[0] == "avg":
                 acols.append(list(zip(v[:, slot[1]].tolist(), vi[:, slot[2]].tolist())))
+            elif slot[0] == "distinct":
+                if distinct_sizes:
+                    acols.append([DistinctSize(c) for c in vi[:, slot[1]].tolist()])
+                else:
+                    acols.append(self.distinct_sets(slot[1], slot[2], n))
             elif slot[0] == "range":
                 pr = pairs[:n * nnat * 2].reshape(n, nnat, 2)
                 acols.append(list(zip(pr[:, slot[1], 0].tolist(), pr[:, slot[1], 1].tolist())))
@@ -411,7 +440,8 @@ class QueryResult:
                 gc.enable()
 
     def rows(self) -> List[tuple]:
-        return reduce_rows(self.qc, self.groups())
+        # a library-executed DISTINCTCOUNT: the counts come with the fetch, the value sets stay on the device
+        return reduce_rows(self.qc, self.groups(distinct_sizes=True))
 
     def destroy(self) -> None:
         if self._h:
@@ -431,11 +461,20 @@ class ServerQueryExecutor:
     server_trim: apply the server's combine table to GROUP BY results like GroupByCombineOperator's
     IndexedTable (LIMIT groups without ORDER BY; the top max(5 * LIMIT, minServerGroupTrimSize) by the
     ORDER BY otherwise; pinot_amd_query_set_result_limit). Off by default: every group is returned,
-    which is what a multi-server broker reduce over exact partials wants."""
+    which is what a multi-server broker reduce over exact partials wants.
 
-    def __init__(self, use_inverted_index: bool = True, server_trim: bool = False):
+    distinct_count: how a query with DISTINCTCOUNT aggregations runs. "mirror" (default): split here into the
+    base query and one (group, value) query per DISTINCTCOUNT, every pair fetched and folded into Python sets
+    (DistinctCountResult; the path multi-GPU merges use). "native": the whole query goes to the library, which
+    runs the same queries and folds them on the device (PINOT_AMD_AGG_DISTINCTCOUNT); rows() then fetches only
+    the counts, groups() the value sets as CSR."""
+
+    def __init__(self, use_inverted_index: bool = True, server_trim: bool = False, distinct_count: str = "mirror"):
+        if distinct_count not in ("mirror", "native"):
+            raise ValueError(f"distinct_count must be 'mirror' or 'native', not {distinct_count!r}")
         self.use_inverted_index = use_inverted_index
         self.server_trim = server_trim
+        self.distinct_count = distinct_count
 
     def filter_doc_ids(self, query, segments: Sequence[ImmutableSegment], stream=None) -> List[np.ndarray]:
         """FilterPlanNode -> BlockDocIdSet: ascending matching docIds of each segment (the filter
@@ -490,6 +529,15 @@ class ServerQueryExecutor:
         its global key space (dist.global_key_space: the union of every rank's dictionaries), so that
         every rank's dense group table indexes the same groups."""
         qc = parse_sql(query) if isinstance(query, str) else query
+        if any(a.func == "DISTINCTCOUNT" for a in qc.aggregations) and self.distinct_count == "native":
+            if key_space is not None:
+                raise _lib.PinotAmdError("distinct_count='native' takes no key_space: results of several ranks merge "
+                                         "their value sets by union on the mirror path (distinct_count='mirror', "
+                                         "DistinctCountResult.results())")
+            for a in qc.aggregations:
+                if a.func == "DISTINCTCOUNT" and (a.expr is not None or a.column == "*"):
+                    raise ValueError("DISTINCTCOUNT takes one column")
+            return self._execute(qc, segments, stream, None)
         if any(a.func == "DISTINCTCOUNT" for a in qc.aggregations):
             # the device queries run untrimmed (a result limit on a (group, value) sub-query would cut value
             # sets); the server's combine table applies to the folded groups (DistinctCountResult.groups)
@@ -567,6 +615,11 @@ class ServerQueryExecutor:
             for a in qc.aggregations:
                 if a.func == "AVG":
                     agg_slots.append(("avg", add("SUM", a.column, a.expr), add("COUNT", "*")))
+                elif a.func == "DISTINCTCOUNT":  # the library folds the value sets (distinct_count="native")
+                    col = first.columns.get(a.column)
+                    if col is None:
+                        raise _lib.PinotAmdError(f"unknown column {a.column!r} in segment {first.name}")
+                    agg_slots.append(("distinct", add("DISTINCTCOUNT", a.column), col.stored_type))
                 elif a.func == "MINMAXRANGE":  # MinMaxRangePair (min, max), NaN-skipping, in the library
                     agg_slots.append(("range", add("MINMAXRANGE", a.column, a.expr)))
                 else:

@@ -586,6 +586,42 @@ def fold_distinct_count(qc: QueryContext, base_groups: dict, sub_groups: Sequenc
     return out
 
 
+def sets_from_csr(offsets, values, stored_type: str, strings=None) -> List[frozenset]:
+    """The per-group DISTINCTCOUNT partials from the library's CSR (pinot_amd_result_fetch_distinct_values):
+    offsets[g] .. offsets[g + 1] delimit group g's entries of `values`, each an int64 in fetch's key encoding
+    (the value for INT / LONG, the double's bits for FLOAT / DOUBLE, an index into `strings` for STRING). Returns
+    one frozenset of distinct_value(v) per group -- what fold_distinct_count builds from the (group, value)
+    pairs -- and [] for no groups. A pure function of its arguments (no device)."""
+    off = np.asarray(offsets, dtype=np.int64)
+    vals = np.ascontiguousarray(np.asarray(values, dtype=np.int64))
+    if off.size == 0:
+        return []
+    if off[0] != 0 or np.any(np.diff(off) < 0) or off[-1] > vals.size:
+        raise ValueError("malformed CSR offsets")
+    if stored_type == "STRING":
+        if strings is None:
+            raise ValueError("STRING values need their dictionary")
+        items = [strings[i] for i in vals.tolist()]
+    elif stored_type in ("FLOAT", "DOUBLE"):
+        items = [distinct_value(f) for f in vals.view(np.float64).tolist()]
+    else:
+        items = vals.tolist()
+    o = off.tolist()
+    return [frozenset(items[o[g]:o[g + 1]]) for g in range(len(o) - 1)]
+
+
+class DistinctSize:
+    """A DISTINCTCOUNT partial known only by its size (QueryResult.rows() of a natively executed query reads the
+    counts, not the sets): final_value takes its len()."""
+    __slots__ = ("n",)
+
+    def __init__(self, n: int):
+        self.n = int(n)
+
+    def __len__(self):
+        return self.n
+
+
 def _dict_order(v):
     """A group-by value's position key in its (merged) dictionary's order: numbers ascending with
     Double.compare semantics for floats (-0.0 before 0.0, NaN last), strings by UTF-16 code units."""
