@@ -117,6 +117,13 @@ int64_t pinot_amd_segment_device_bytes(const pinot_amd_segment* seg);
 /* Device pointer to a staged column's forward-index values (fixed-bit stream, raw values at
  * rawDataStart, or sorted pairs) — for the low-level entry points below. */
 const void* pinot_amd_segment_column_fwd(const pinot_amd_segment* seg, const char* column);
+/* The packed twin staging built for a raw INT / LONG column (value - base bit-packed in two planes; the
+ * streaming scan kernels read it instead of the raw bytes, PINOT_AMD_PACKED=0 builds none). Returns 1 and fills
+ * the low plane's bits per doc (0, 16, 32), the high plane's (0..16), the base (the column's minimum) and the
+ * twin's HBM bytes (padding included; they count in pinot_amd_segment_device_bytes); 0 when the column has no
+ * twin; < 0 on error. Any out pointer may be NULL. */
+int pinot_amd_segment_column_packed_info(const pinot_amd_segment* seg, const char* column, int32_t* lo_bits,
+                                         int32_t* hi_bits, int64_t* base, int64_t* twin_bytes);
 
 /* ------------------------------------------------------------------------------------------------
  * Low-level operators (one per reference class), device in / device out.
@@ -365,12 +372,17 @@ const char* pinot_amd_result_distinct_string(pinot_amd_result* r, int32_t agg_in
  * (sequential / first-doc), and " xN" when the batch ran as N shape launches. */
 const char* pinot_amd_result_kernel_info(pinot_amd_result* r);
 /* Algorithmic HBM bytes of the last execution (the roofline numerator): every decoded column once
- * (fixed-bit columns at their bit width, raw columns at their value width); under an inverted-index
+ * (fixed-bit columns at their bit width, raw columns at their value width, or at their packed twin's width
+ * where the plan streams the twin: pinot_amd_result_packed_info); under an inverted-index
  * gate only the rows that pass it; selection-vector plans: the filter columns of every doc, 16 B per
  * vector entry (written + read) and the gathered columns of the matches; plus, per inverted-index leaf,
  * the selected bitmaps' serialized bytes and -- only when the expansion writes one -- the dense docId
  * bitset written and read once (the fused -fwselect plan writes none). */
 int pinot_amd_result_algorithmic_bytes(pinot_amd_result* r, double* h_bytes);
+/* Which raw columns the plan's streaming kernels read through their packed twins: "column:lo+hi" (plane bits
+ * per doc) per column and shape launch, launches separated by ";", "" when none. Such columns count in
+ * pinot_amd_result_algorithmic_bytes at (lo + hi) / 8 bytes per row. */
+const char* pinot_amd_result_packed_info(pinot_amd_result* r);
 /* Host planning time of the execute that built this result, per phase, as "phase=ms;..." (raw_keys:
  * derived dictionaries of raw GROUP BY columns; leaves: per-segment predicate resolution; keys_probe:
  * merged key space + the plan-time match-count probe; plan: accumulators, plan kind, descriptors;

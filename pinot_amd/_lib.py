@@ -63,6 +63,8 @@ SIGNATURES = {
     "pinot_amd_segment_num_docs": (C.c_int64, [_P]),
     "pinot_amd_segment_device_bytes": (C.c_int64, [_P]),
     "pinot_amd_segment_column_fwd": (C.c_void_p, [_P, C.c_char_p]),
+    "pinot_amd_segment_column_packed_info": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pinot_amd_fwd_read_dict_ids": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, _P]),
     "pinot_amd_fwd_pack_dict_ids": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P]),
     "pinot_amd_fwd_read_raw": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, _P]),
@@ -108,6 +110,7 @@ SIGNATURES = {
     "pinot_amd_result_last_kernel_ms": (C.c_int, [_P, C.POINTER(C.c_double)]),
     "pinot_amd_result_kernel_info": (C.c_char_p, [_P]),
     "pinot_amd_result_algorithmic_bytes": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    "pinot_amd_result_packed_info": (C.c_char_p, [_P]),
 }
 
 _lib = None

@@ -50,6 +50,16 @@ struct DevColumn {
   const void* dict;        // dictionary values, native LE array of the value type (dict columns)
   const int32_t* remap;    // dictId -> ordinal in the query's merged key space (group-by columns)
   int32_t enc, type, bits, card;
+  // Packed twin of a raw INT / LONG column (frame of reference, built at staging; null / 0 without one):
+  // value = for_base + ((high field << for_lo_bits) | low element) in unsigned 64-bit arithmetic. for_lo: the
+  // little-endian low plane, for_lo_bits (0, 16 or 32) per doc; for_hi: the high plane, for_hi_bits (0..16) per doc
+  // in the big-endian fixed-bit stream. `data` stays the raw values: random-access readers (the gather pass) of
+  // the same launch read those. A launch streams the twin when its JitSlot says so (JitSlot::packed).
+  const uint8_t* for_lo;
+  const uint8_t* for_hi;
+  int64_t for_base;
+  int32_t for_lo_bits, for_hi_bits;
+  int32_t for_twin, for_pad;         // for_twin: 1 when the column has a twin (both widths 0: a constant column)
 };
 
 struct DevLeaf {

@@ -36,6 +36,8 @@ hipError_t launch_init_acc(uint64_t* d_acc, const DevQuery& q, int64_t num_keys,
 hipError_t launch_sext_hi(uint64_t* d_acc, int64_t n, const int32_t* arrs, int32_t narr, hipStream_t st);
 hipError_t launch_raw_int_minmax(const uint8_t* be, int type, int64_t n, long long* out, hipStream_t st);
 hipError_t launch_fingerprint(const void* p, size_t bytes, unsigned long long* out, hipStream_t st);
+hipError_t launch_for_pack(const uint8_t* be, int type, int64_t n, unsigned long long base, int lo_bits, int hi_bits,
+                           uint8_t* lo, uint8_t* hi, hipStream_t st);
 hipError_t launch_trim(const unsigned long long* keys, int64_t cap, int nw_seg, const uint64_t* acc, int fd_acc,
                        int32_t nsegs, int64_t limit, const int64_t* bucket_base, uint32_t* hist,
                        unsigned long long* seg_distinct, int64_t* bstar, int64_t* rank, unsigned long long* bitmap,
@@ -161,6 +163,7 @@ static const std::set<std::string>& kept_knobs() {
       "PINOT_AMD_HASH_TABLE_BYTES",
       "PINOT_AMD_INV_POLICY",
       "PINOT_AMD_NARROW_SUMS",
+      "PINOT_AMD_PACKED",
       "PINOT_AMD_PARTITIONED",
       "PINOT_AMD_PART_CAP_SCALE",
       "PINOT_AMD_PREFETCH",
@@ -433,6 +436,13 @@ struct Column {
   // staged raw values; bounds which integer sums fit 64-bit partial accumulators
   bool has_range = false;
   int64_t vmin = 0, vmax = 0;
+  // Packed twin of a raw INT / LONG column (frame of reference, DevColumn::for_*): value - vmin split into a
+  // little-endian low plane of for_lo_bits (0, 16, 32) and a fixed-bit high plane of for_hi_bits (0..16, rounded up
+  // the ladder of for_ladder()). Built at staging when for_lo_bits + for_hi_bits <= 3/4 of the stored width; the raw
+  // bytes in `fwd` stay (random-access readers and PINOT_AMD_PACKED=0 plans read them).
+  bool has_twin = false;
+  int32_t for_lo_bits = 0, for_hi_bits = 0;
+  DevBuf for_lo, for_hi;
   // inverted index
   DevBuf inv;
   DevBuf inv_conts;
@@ -922,7 +932,8 @@ int pinot_amd_segment_destroy(pinot_amd_segment* seg) {
   if (seg) drop_segment_caches(seg->uid);  // merged key spaces, remaps and prepared plans over it
   if (seg) {
     std::lock_guard<std::mutex> g(g_print_mu);
-    for (auto& kv : seg->cols) g_prints.erase(kv.second->fwd.p);
+    for (auto& kv : seg->cols)
+      for (const void* p : {kv.second->fwd.p, kv.second->for_lo.p, kv.second->for_hi.p}) g_prints.erase(p);
   }
   delete seg;
   return 0;
@@ -935,6 +946,67 @@ const void* pinot_amd_segment_column_fwd(const pinot_amd_segment* seg, const cha
   if (!seg || !column) return nullptr;
   auto it = seg->cols.find(column);
   return it == seg->cols.end() ? nullptr : it->second->fwd.p;
+}
+
+// PINOT_AMD_PACKED=0: no packed twins are built at staging and no plan reads one
+static bool packed_enabled() {
+  const char* v = knob("PINOT_AMD_PACKED");
+  return !(v && strcmp(v, "0") == 0);
+}
+
+// The high plane's width ladder: widths round up to 1, 2, 4, 8, 10, 12 or 16 bits. Each of these decodes from a
+// one- or two-dword window (fixed_bit4_1 / fixed_bit4_c2), and segments whose ranges differ a little share one
+// launch shape.
+static int for_ladder(int bits) {
+  static const int kLadder[] = {0, 1, 2, 4, 8, 10, 12, 16};
+  for (int w : kLadder)
+    if (bits <= w) return w;
+  return -1;
+}
+// plane widths of a delta of b significant bits; false when b > 48
+static bool for_planes(int b, int* lo, int* hi) {
+  *lo = b <= 16 ? 0 : b <= 32 ? 16 : 32;
+  *hi = for_ladder(b - *lo);
+  return *hi >= 0;
+}
+
+// The packed twin of a staged raw INT / LONG column with its range known (vmin / vmax over nd > 0 docs).
+static int build_packed_twin(Column& c, int64_t nd) {
+  if (!packed_enabled()) return 0;
+  const uint64_t range = (uint64_t)c.vmax - (uint64_t)c.vmin;  // unsigned: vmax - vmin may exceed INT64_MAX
+  const int b = range ? 64 - __builtin_clzll(range) : 0;
+  int lo = 0, hi = 0;
+  if (!for_planes(b, &lo, &hi)) return 0;
+  if ((lo + hi) * 4 > value_size(c.type) * 8 * 3) return 0;  // worth it at <= 3/4 of the stored width
+  if (lo > 0) {
+    if (int rc = c.for_lo.alloc((size_t)nd * (lo / 8) + kPadBytes)) return rc;
+    HIP_OK(hipMemset(c.for_lo.p, 0, c.for_lo.n));
+  }
+  if (hi > 0) {
+    if (int rc = c.for_hi.alloc((size_t)((nd * hi + 7) / 8) + kPadBytes)) return rc;
+    HIP_OK(hipMemset(c.for_hi.p, 0, c.for_hi.n));
+  }
+  if (lo > 0 || hi > 0)
+    HIP_OK(launch_for_pack((const uint8_t*)c.fwd.p, c.type, nd, (unsigned long long)c.vmin, lo, hi, (uint8_t*)c.for_lo.p,
+                           (uint8_t*)c.for_hi.p, nullptr));
+  c.has_twin = true;
+  c.for_lo_bits = lo;
+  c.for_hi_bits = hi;
+  return 0;
+}
+
+int pinot_amd_segment_column_packed_info(const pinot_amd_segment* seg, const char* column, int32_t* lo_bits,
+                                         int32_t* hi_bits, int64_t* base, int64_t* twin_bytes) {
+  if (!seg || !column) return fail(PINOT_AMD_EINVAL, "column_packed_info: bad arguments");
+  auto it = seg->cols.find(column);
+  if (it == seg->cols.end()) return fail(PINOT_AMD_EINVAL, "column_packed_info: no column %s", column);
+  const Column& c = *it->second;
+  if (!c.has_twin) return 0;
+  if (lo_bits) *lo_bits = c.for_lo_bits;
+  if (hi_bits) *hi_bits = c.for_hi_bits;
+  if (base) *base = c.vmin;
+  if (twin_bytes) *twin_bytes = (int64_t)(c.for_lo.n + c.for_hi.n);
+  return 1;
 }
 
 int pinot_amd_segment_add_column(pinot_amd_segment* seg, const pinot_amd_column_spec* spec) {
@@ -1066,18 +1138,20 @@ int pinot_amd_segment_add_column(pinot_amd_segment* seg, const pinot_amd_column_
     c->has_range = true;
     c->vmin = got[0];
     c->vmax = got[1];
+    if (int rc2 = build_packed_twin(*c, nd)) return rc2;
   }
   if (spec->h_inverted && spec->inverted_size) {
     if (c->enc == ENC_RAW) return fail(PINOT_AMD_EUNSUPPORTED, "column %s: inverted index on raw column", spec->name);
     rc = build_inverted_directory(*c, (const uint8_t*)spec->h_inverted, spec->inverted_size);
     if (rc) return rc;
   }
-  seg->device_bytes += (int64_t)(c->fwd.n + c->dict.n + c->inv.n + c->inv_conts.n);
-  if (c->fwd.p) {
-    StagedPrint sp{c->fwd.n, 0};
-    if (int rc2 = device_fingerprint(c->fwd.p, sp.bytes, &sp.print)) return rc2;
+  seg->device_bytes += (int64_t)(c->fwd.n + c->dict.n + c->inv.n + c->inv_conts.n + c->for_lo.n + c->for_hi.n);
+  for (const DevBuf* b : {&c->fwd, &c->for_lo, &c->for_hi}) {
+    if (!b->p) continue;
+    StagedPrint sp{b->n, 0};
+    if (int rc2 = device_fingerprint(b->p, sp.bytes, &sp.print)) return rc2;
     std::lock_guard<std::mutex> g(g_print_mu);
-    g_prints[c->fwd.p] = sp;
+    g_prints[b->p] = sp;
   }
   seg->cols[c->name] = std::move(c);
   return 0;
@@ -1448,6 +1522,7 @@ struct Launch {
   DevPartition part{};
   int64_t docs = 0, tiles = 0;
   double col_bytes = 0;  // algorithmic bytes of the launch's decoded columns over all its docs
+  uint32_t packed = 0;   // bit sl: the launch's streaming kernels read slot sl's packed twin (JitSlot::packed)
   bool gated = false;    // an inverted-index gate clause: columns are read only where it passes
   // selection-vector plan (late materialisation): select pass over the filter columns, gather pass
   bool select = false, word_select = false;
@@ -1513,6 +1588,7 @@ struct pinot_amd_result {
   std::deque<Launch> launches;  // deque: Launch holds device buffers and is never moved
   std::vector<std::unique_ptr<DevBuf>> owned;  // leaf sets, remaps, bitsets
   bool filter_gate = false;  // the fused scan loads key / value columns behind its filter (JitPlan::filter_gate)
+  std::vector<std::string> slot_names;  // column of each slot (pinot_amd_result_packed_info)
   // inverted index leaves to (re)build each execution: (segment, leaf, container selection)
   struct InvLeaf {
     int seg;
@@ -3511,6 +3587,8 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
   clk.mark("hash_sizes");
   // ---- device segments (one DevSegment per segment; tile_begin / key_seg set per launch) ----
   std::vector<DevSegment> hsegs(n);
+  const bool packed_on = packed_enabled();
+  r->slot_names = slot_cols;
   for (int si = 0; si < n; ++si) {
     DevSegment& ds = hsegs[si];
     memset(&ds, 0, sizeof(ds));
@@ -3524,6 +3602,14 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
       dc.type = c.type;
       dc.bits = c.bits;
       dc.card = c.card;
+      if (c.has_twin && packed_on) {
+        dc.for_twin = 1;
+        dc.for_lo = (const uint8_t*)c.for_lo.p;
+        dc.for_hi = (const uint8_t*)c.for_hi.p;
+        dc.for_base = c.vmin;
+        dc.for_lo_bits = c.for_lo_bits;
+        dc.for_hi_bits = c.for_hi_bits;
+      }
     }
     for (size_t j = 0; j < Q.group_by.size(); ++j) {
       const Column& c = *segs[si]->cols.at(Q.group_by[j]);
@@ -3761,6 +3847,10 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
     }
   auto slot_bpr = [](const DevColumn& c) -> double {
     return c.enc == ENC_FIXED_BIT ? c.bits / 8.0 : c.enc == ENC_RAW ? (double)value_size(c.type) : 0.0;
+  };
+  // bytes per row a streaming kernel reads of a column: the packed twin's planes where the launch uses it
+  auto stream_bpr = [&](const DevColumn& c, bool packed) -> double {
+    return packed ? (c.for_lo_bits + c.for_hi_bits) / 8.0 : slot_bpr(c);
   };
   const char* sel_env = knob("PINOT_AMD_SELECT");
   // (a partitioned plan qualifies too: when its filter keeps few docs, the gather adds them straight into
@@ -4006,12 +4096,47 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
           sig += std::to_string(hsegs[si].cols[sl].enc == ENC_FIXED_BIT && hsegs[si].cols[sl].bits <= 15 ? hsegs[si].cols[sl].bits : 0) + ",";
         return sig;
       };
+      // Packed twins: a raw INT / LONG slot streams its twin when every segment of the group has one. The planes'
+      // widths are compile-time constants of the kernel, so they join the shape signature; a slot whose widths
+      // would split the group into more than 3 shapes reads its raw bytes instead (the slot with the most
+      // distinct widths first).
+      uint32_t packed = 0;
+      for (int sl = 0; sl < nslots; ++sl) {
+        bool all = packed_on && hsegs[group[0]].cols[sl].enc == ENC_RAW;
+        for (int si : group) all &= hsegs[si].cols[sl].for_twin != 0;
+        if (all) packed |= 1u << sl;
+      }
+      auto for_sig = [&](int si, int sl) {
+        return std::to_string(hsegs[si].cols[sl].for_lo_bits) + "." + std::to_string(hsegs[si].cols[sl].for_hi_bits);
+      };
       std::map<std::string, std::vector<int>> by_bits;
       std::vector<std::string> bits_order;
-      for (int si : group) {
-        const std::string sig = bits_sig(si);
-        if (!by_bits.count(sig)) bits_order.push_back(sig);
-        by_bits[sig].push_back(si);
+      auto split = [&]() {
+        by_bits.clear();
+        bits_order.clear();
+        for (int si : group) {
+          std::string sig = bits_sig(si);
+          for (int sl = 0; sl < nslots; ++sl)
+            if (packed >> sl & 1u) sig += "f" + for_sig(si, sl) + ",";
+          if (!by_bits.count(sig)) bits_order.push_back(sig);
+          by_bits[sig].push_back(si);
+        }
+      };
+      split();
+      while (bits_order.size() > 3 && packed) {
+        int worst = -1;
+        size_t worst_n = 1;
+        for (int sl = 0; sl < nslots; ++sl) {
+          if (!(packed >> sl & 1u)) continue;
+          std::set<std::string> widths;
+          for (int si : group) widths.insert(for_sig(si, sl));
+          if (widths.size() > worst_n) worst = sl, worst_n = widths.size();
+        }
+        // the fixed-bit widths alone make the many shapes: the one run-time-width launch below streams the
+        // twins whose widths agree
+        if (worst < 0) break;
+        packed &= ~(1u << worst);
+        split();
       }
       std::vector<std::vector<int>> parts;
       if (bits_order.size() <= 3) {
@@ -4024,6 +4149,7 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
         Launch& L = r->launches.back();
         L.segs = part_segs;
         L.batch = b;
+        L.packed = packed;
       }
     }
   }
@@ -4159,6 +4285,20 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
           if (d.cols[sl].bits != js.bits) js.bits = 0;
         if (js.bits > 15 || generic_bits) js.bits = 0;
       }
+      if (L.packed >> sl & 1u) {  // the twin's plane widths: the same in every segment of the launch
+        // (a select pass streams the filter columns only; its gather reads the other columns' raw bytes)
+        bool same = enc == ENC_RAW && !(jp.select && !leaf_slot[sl]);
+        for (auto& d : ls)
+          same &= d.cols[sl].for_twin && d.cols[sl].for_lo_bits == ls[0].cols[sl].for_lo_bits &&
+                  d.cols[sl].for_hi_bits == ls[0].cols[sl].for_hi_bits;
+        if (same) {
+          js.packed = 1;
+          js.for_lo = ls[0].cols[sl].for_lo_bits;
+          js.for_hi = ls[0].cols[sl].for_hi_bits;
+        } else {
+          L.packed &= ~(1u << sl);
+        }
+      }
       jp.slots.push_back(js);
     }
     for (size_t k = 0; k < order.size(); ++k) {
@@ -4211,7 +4351,9 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
       for (size_t sl = 0; sl < jp.slots.size(); ++sl) {
         if (jp.select && !leaf_slot[sl]) continue;  // a select pass streams the filter columns only
         const JitSlot& js = jp.slots[sl];
-        bpr += js.enc == ENC_FIXED_BIT ? (js.bits > 0 ? js.bits : 16) / 8.0 : js.enc == ENC_RAW ? value_size(js.type) : 0.0;
+        bpr += js.enc == ENC_FIXED_BIT ? (js.bits > 0 ? js.bits : 16) / 8.0
+               : js.packed            ? (js.for_lo + js.for_hi) / 8.0  // the bytes the launch streams
+               : js.enc == ENC_RAW    ? value_size(js.type) : 0.0;
       }
       jp.depth = bpr <= 0 ? 1 : (int)std::min(4.0, std::max(1.0, std::ceil(4096.0 / (256.0 * bpr))));
       // a select step of G tiles loads G tiles per register set: the same bytes in flight with 1/G the sets
@@ -4224,8 +4366,11 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
       if (const char* pw = knob("PINOT_AMD_WAVES_PER_EU")) jp.waves_per_eu = std::max(0, std::min(8, atoi(pw)));
       // non-temporal column loads for wide-row fused scans (configs[1]: 3.58 -> 3.51 ms per 1B rows); the
       // narrow SSB select passes measured 1-3 % slower with them, the partitioned scatter 10 % slower
+      // bpr counts the bytes the launch streams (packed twins at their plane widths): configs[1] with twins is
+      // 15.375 B/row and still gains from the hint (2.665 -> 2.588 ms per 1B rows, profiles/r07/sweep_packed.txt),
+      // so the bound sits at 15 B/row; rows between the SSB passes' widths and 15 B were not measured
       jp.nt_loads = env_is("PINOT_AMD_NT_LOADS", "1") ||
-                    (!env_is("PINOT_AMD_NT_LOADS", "0") && bpr >= 16.0 && !jp.partitioned && !jp.select);
+                    (!env_is("PINOT_AMD_NT_LOADS", "0") && bpr >= 15.0 && !jp.partitioned && !jp.select);
       // XCD-aware tile ranges where blocks read per-segment tables beside the columns: the admission bitmaps
       // (128 KiB per segment for configs[3]) thrashed each XCD's L2 when its blocks spanned every segment
       // (default-limit configs[3] scatter: 20.1 -> 8.8 GB fetched per 400M rows, 4.87 -> 4.15 ms per plan;
@@ -4270,9 +4415,7 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
     {  // algorithmic bytes: each decoded column once (fixed-bit at its width, raw at its value width)
       for (size_t k = 0; k < L.segs.size(); ++k)
         for (int sl = 0; sl < nslots; ++sl) {
-          const DevColumn& dc = ls[k].cols[sl];
-          const double bpr = dc.enc == ENC_FIXED_BIT ? dc.bits / 8.0 : dc.enc == ENC_RAW ? (double)value_size(dc.type) : 0.0;
-          L.col_bytes += bpr * (double)ls[k].num_docs;
+          L.col_bytes += stream_bpr(ls[k].cols[sl], L.packed >> sl & 1u) * (double)ls[k].num_docs;
         }
       std::vector<int> gate(nclauses, 1), has(nclauses, 0);
       for (const JitLeaf& jl : jp.leaves) {
@@ -4284,7 +4427,7 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
         L.fgate = true;
         for (size_t k = 0; k < L.segs.size(); ++k)
           for (int sl = 0; sl < nslots; ++sl) {
-            const double bpr = slot_bpr(ls[k].cols[sl]);
+            const double bpr = stream_bpr(ls[k].cols[sl], L.packed >> sl & 1u);  // both parts stream the twins
             if (leaf_slot[sl]) L.filter_bytes += bpr * (double)ls[k].num_docs;
             if (value_slot[sl] && k == 0) L.value_bpr += bpr;
           }
@@ -4475,9 +4618,9 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
       if (const char* e = knob("PINOT_AMD_GATHER_BLOCKS")) L.gather_grid = std::max(1, std::min(L.gather_grid, atoi(e)));
       for (size_t k = 0; k < L.segs.size(); ++k)
         for (int sl = 0; sl < nslots; ++sl) {
-          const double bpr = slot_bpr(ls[k].cols[sl]);
-          if (leaf_slot[sl]) L.filter_bytes += bpr * (double)ls[k].num_docs;
-          if (value_slot[sl] && k == 0) L.value_bpr += bpr;
+          // the select pass streams the filter columns (their twins where used); the gather reads raw bytes
+          if (leaf_slot[sl]) L.filter_bytes += stream_bpr(ls[k].cols[sl], L.packed >> sl & 1u) * (double)ls[k].num_docs;
+          if (value_slot[sl] && k == 0) L.value_bpr += slot_bpr(ls[k].cols[sl]);
         }
       // Vector chunk a wave reserves at a time (plan-time counts): a power of two in [256, 4096] for the
       // tile-level select, [64, 4096] for the word-level one; runs split across chunks in both.
@@ -5113,6 +5256,25 @@ int pinot_amd_result_algorithmic_bytes(pinot_amd_result* r, double* h_bytes) {
     }
   *h_bytes = b;
   return 0;
+}
+
+const char* pinot_amd_result_packed_info(pinot_amd_result* r) {
+  if (!r) return "";
+  static thread_local std::string info;
+  info.clear();
+  for (size_t li = 0; li < r->launches.size(); ++li) {
+    const Launch& L = r->launches[li];
+    if (li) info += ";";
+    bool first = true;
+    for (size_t sl = 0; sl < r->slot_names.size() && !L.h_segs.empty(); ++sl) {
+      if (!(L.packed >> sl & 1u)) continue;
+      const DevColumn& dc = L.h_segs[0].cols[sl];
+      info += (first ? "" : ",") + r->slot_names[sl] + ":" + std::to_string(dc.for_lo_bits) + "+" + std::to_string(dc.for_hi_bits);
+      first = false;
+    }
+  }
+  if (info.find_first_not_of(';') == std::string::npos) info.clear();
+  return info.c_str();
 }
 
 static std::string kernel_info_of(pinot_amd_result* r) {

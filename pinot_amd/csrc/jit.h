@@ -25,6 +25,12 @@ struct JitSlot {
   int type;      // T_* value type
   int bits = 0;  // FIXED_BIT: bit width when every segment of the batch agrees (<= 15), else 0
   int dict_regs = 0;  // dictionary of <= 64 entries in every segment: looked up across lanes (ds_bpermute)
+  // ENC_RAW INT / LONG whose streaming loads read the column's packed twin (DevColumn::for_*) in every segment of
+  // the launch: the low plane's width (0, 16, 32) and the high plane's (0..16), compile-time constants of the
+  // kernel. The decoded V<slot>[4] are the same int32_t / int64_t values the raw bytes give; the gather pass
+  // (random access) keeps reading the raw bytes.
+  int packed = 0;
+  int for_lo = 0, for_hi = 0;
 };
 struct JitLeaf {
   int slot;        // -1: reads no column (docId range / bitset / constant)

@@ -1,8 +1,11 @@
 // kernels.hip — gfx950 kernels for Pinot's segment scan / filter / aggregation / group-by.
 //
 // Layout in HBM: every column keeps the bytes Pinot writes for it — the fixed-bit
-// forward index as the big-endian MSB-first bit stream, raw values big-endian — so nothing is
-// transcoded at staging time; the kernels byte-swap in registers (v_perm_b32).
+// forward index as the big-endian MSB-first bit stream, raw values big-endian — and the kernels
+// byte-swap in registers (v_perm_b32). The one transcode at staging: a raw INT / LONG column whose value range
+// fits 3/4 of its stored width also gets a packed twin (for_pack_kernel: value - min in a little-endian low
+// plane of 0 / 16 / 32 bits and a fixed-bit high plane of <= 16 bits), which the streaming scan kernels read
+// instead of the raw bytes; the raw bytes stay for the random-access readers.
 //
 // The fused scan (filter + group key + aggregation) is generated per query shape and compiled with
 // hipRTC (jit.cpp); this file holds the fixed kernels around it: accumulator initialisation, the
@@ -1928,6 +1931,55 @@ hipError_t launch_raw_int_minmax(const uint8_t* be, int type, int64_t n, long lo
   if (g > 2048) g = 2048;
   if (g < 1) g = 1;
   hipLaunchKernelGGL(raw_int_minmax_kernel, dim3(g), dim3(kBlock), 0, st, be, type, n, out);
+  return hipGetLastError();
+}
+
+// Packed twin of a raw INT / LONG column (frame of reference): delta = value - base as an unsigned 64-bit
+// difference, split in two planes. Low plane: the delta's low lo_bits (0, 16 or 32) as a little-endian array, one
+// element per doc. High plane: the next hi_bits (0..16) in Pinot's big-endian MSB-first fixed-bit stream, so the
+// fixed-bit decoders read it. One thread packs 32 consecutive docs: 32 x hi_bits bits are hi_bits whole dwords, so
+// no two threads share a word. Docs past n pack as zero; the buffers hold the dwords of the last thread's group.
+__global__ void for_pack_kernel(const uint8_t* __restrict__ be, int type, int64_t n, unsigned long long base, int lo_bits,
+                                int hi_bits, uint8_t* __restrict__ lo, uint32_t* __restrict__ hi) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t d0 = g * 32;
+  if (d0 >= n) return;
+  uint64_t acc = 0;  // bits of the stream not yet written, right-aligned
+  int nacc = 0;
+  uint32_t* out = hi + g * hi_bits;
+  for (int k = 0; k < 32; ++k) {
+    const int64_t d = d0 + k;
+    uint64_t delta = 0;
+    if (d < n) {
+      uint64_t v;
+      if (type == T_INT) {
+        v = (uint64_t)(int64_t)(int32_t)__builtin_bswap32(*reinterpret_cast<const uint32_t*>(be + 4 * d));
+      } else {
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(be + 8 * d);
+        v = ((uint64_t)__builtin_bswap32(w[0]) << 32) | __builtin_bswap32(w[1]);
+      }
+      delta = v - base;
+      if (lo_bits == 16) reinterpret_cast<uint16_t*>(lo)[d] = (uint16_t)delta;
+      else if (lo_bits == 32) reinterpret_cast<uint32_t*>(lo)[d] = (uint32_t)delta;
+    }
+    if (hi_bits > 0) {
+      const uint64_t h = (delta >> lo_bits) & ((1ull << hi_bits) - 1ull);
+      acc = (acc << hi_bits) | h;
+      nacc += hi_bits;
+      if (nacc >= 32) {
+        *out++ = __builtin_bswap32((uint32_t)(acc >> (nacc - 32)));
+        nacc -= 32;
+      }
+    }
+  }
+}
+
+hipError_t launch_for_pack(const uint8_t* be, int type, int64_t n, unsigned long long base, int lo_bits, int hi_bits,
+                           uint8_t* lo, uint8_t* hi, hipStream_t st) {
+  const int64_t groups = (n + 31) / 32;
+  if (groups <= 0) return hipSuccess;
+  hipLaunchKernelGGL(for_pack_kernel, dim3(grid_for(groups, kBlock)), dim3(kBlock), 0, st, be, type, n, base, lo_bits,
+                     hi_bits, lo, (uint32_t*)hi);
   return hipGetLastError();
 }
 

@@ -84,6 +84,17 @@ class ImmutableSegment:
     def device_bytes(self) -> int:
         return int(lib().pinot_amd_segment_device_bytes(self._h))
 
+    def packed_info(self, column: str):
+        """The column's packed twin as {'lo_bits', 'hi_bits', 'base', 'bytes'}, or None without one."""
+        lo, hi, base, nbytes = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+        rc = lib().pinot_amd_segment_column_packed_info(self._h, column.encode(), C.byref(lo), C.byref(hi),
+                                                        C.byref(base), C.byref(nbytes))
+        if rc < 0:
+            raise KeyError(column)
+        if rc == 0:
+            return None
+        return {"lo_bits": lo.value, "hi_bits": hi.value, "base": base.value, "bytes": nbytes.value}
+
     def column_fwd_ptr(self, column: str) -> int:
         p = lib().pinot_amd_segment_column_fwd(self._h, column.encode())
         if not p:
@@ -267,6 +278,11 @@ class QueryResult:
         filter on 4-doc tiles / 64-doc bitset words), 'jit-partitioned', 'jit-hash', 'jit-hash-trim';
         ' xN' when the batch ran as N shape launches."""
         return lib().pinot_amd_result_kernel_info(self._h).decode()
+
+    def packed_info(self) -> str:
+        """Raw columns the plan streamed through their packed twins: 'column:lo+hi' (plane bits per doc) per
+        shape launch, ';' between launches, '' when none."""
+        return lib().pinot_amd_result_packed_info(self._h).decode()
 
     def last_kernel_ms(self) -> float:
         out = C.c_double()
