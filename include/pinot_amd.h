@@ -64,7 +64,25 @@ enum pinot_amd_agg_type { PINOT_AMD_AGG_COUNT = 0, PINOT_AMD_AGG_SUM = 1, PINOT_
                            * column (value identity = its id in the batch's merged dictionary: FLOAT/DOUBLE by
                            * floatToIntBits / doubleToLongBits, one NaN, -0.0 != 0.0); final result the set's
                            * size. See "DISTINCTCOUNT results" below. */
-                          PINOT_AMD_AGG_DISTINCTCOUNT = 7 };
+                          PINOT_AMD_AGG_DISTINCTCOUNT = 7,
+                          /* The other aggregations answered from DISTINCTCOUNT's value-set query, whose rows
+                           * with their COUNT are each group's histogram over the column's distinct values in
+                           * merged-dictionary order (added with pinot_amd_query_add_aggregation_param; one INT /
+                           * LONG / FLOAT / DOUBLE column). See "DISTINCTCOUNT results" below.
+                           * PercentileAggregationFunction.java:79-131,207-252: the group's values as doubles
+                           * over every matching doc, sorted as Arrays.sort(double[]) does (-0.0 < 0.0, NaN
+                           * greatest: the merged dictionary's order); n values: the last for p = 100, else the
+                           * one at index (int) ((double) n * p / 100.0); no matching doc: -inf. */
+                          PINOT_AMD_AGG_PERCENTILE = 8,
+                          /* DistinctSumAggregationFunction.java:83-95: the sum of DISTINCTCOUNT's set as doubles
+                           * (an empty set: 0.0), summed on the device in a fixed order: two executions return
+                           * the same bits. An INT / LONG column is also summed exactly: while the sum fits int64
+                           * the result is that integer rounded once (equal to the reference's sum while its
+                           * partial sums stay below 2^53); FLOAT / DOUBLE: within 1e-12 relative. */
+                          PINOT_AMD_AGG_DISTINCTSUM = 9,
+                          /* DistinctAvgAggregationFunction.java:83-95: that sum over the set's size (0.0 / 0 =
+                           * NaN for an empty set) */
+                          PINOT_AMD_AGG_DISTINCTAVG = 10 };
 
 /* ------------------------------------------------------------------------------------------------
  * Runtime
@@ -197,15 +215,23 @@ int pinot_amd_query_add_predicate(pinot_amd_query* q, int32_t clause, const pino
  * at the first such query (kept for later queries). */
 int pinot_amd_query_add_group_by(pinot_amd_query* q, const char* column);
 /* Aggregation function (column NULL or "*" for COUNT(*)). Returns the aggregation index via out_index.
- * PINOT_AMD_AGG_DISTINCTCOUNT takes a column of any stored type, STRING included (EINVAL for NULL / "*"). */
+ * PINOT_AMD_AGG_DISTINCTCOUNT takes a column of any stored type, STRING included (EINVAL for NULL / "*").
+ * Types above PINOT_AMD_AGG_DISTINCTCOUNT: EINVAL (pinot_amd_query_add_aggregation_param adds them). */
 int pinot_amd_query_add_aggregation(pinot_amd_query* q, int32_t agg_type, const char* column, int32_t* out_index);
+/* The same for every aggregation type, with the function's literal argument: `param` is the percentile of
+ * PINOT_AMD_AGG_PERCENTILE, 0 <= param <= 100 (anything else, NaN included: EINVAL;
+ * AggregationFunctionFactory.java:143,191,534-536), and is ignored for the other types. PERCENTILE, DISTINCTSUM and
+ * DISTINCTAVG take one column (EINVAL for NULL / "*"; a STRING column: EINVAL from pinot_amd_execute). The
+ * percentile is part of no cached plan's identity: queries that differ only in it run the same plans. */
+int pinot_amd_query_add_aggregation_param(pinot_amd_query* q, int32_t agg_type, const char* column, double param,
+                                          int32_t* out_index);
 /* Aggregation over a binary arithmetic transform of two columns (SUM / MIN / MAX / AVG):
  * MultiplicationTransformFunction (times), SubtractionTransformFunction (minus),
  * AdditionTransformFunction (plus) in core/operator/transform/function/. Pinot evaluates these in
  * double; with two INT operands the device sums the exact int64 value (equal to the reference's
  * double sum while partial sums stay below 2^53), otherwise it computes in double as the
  * reference does. Needs the query-specialised (hipRTC) kernel; EUNSUPPORTED without it.
- * DISTINCTCOUNT over an expression: EUNSUPPORTED. */
+ * DISTINCTCOUNT, PERCENTILE, DISTINCTSUM or DISTINCTAVG over an expression: EUNSUPPORTED. */
 enum pinot_amd_expr_op { PINOT_AMD_EXPR_COLUMN = 0, PINOT_AMD_EXPR_MUL = 1, PINOT_AMD_EXPR_SUB = 2,
                          PINOT_AMD_EXPR_ADD = 3 };
 int pinot_amd_query_add_aggregation_expr(pinot_amd_query* q, int32_t agg_type, int32_t expr_op, const char* column_a,
@@ -353,16 +379,37 @@ int pinot_amd_result_merge_groups(pinot_amd_result* r, const uint64_t* d_keys, c
  * Every read fails with EINVAL when the self-check of the base or of a value-set query failed, or when a
  * (group, value) pair belongs to no group of a base query that could not have trimmed.
  *
+ * PERCENTILE, DISTINCTSUM and DISTINCTAVG are answered from the same value-set query (every such aggregation on
+ * one column shares it, whatever the percentile: kernel_info keeps one " +distinct(<column>:...)" per column), with
+ * the same rules (groups, numGroupsLimit, kMaxGroupCols, segment-level trims, the result calls above). The
+ * value-set query's COUNT rides through the fold: a percentile is a rank selection in each group's cumulative doc
+ * counts, DISTINCTSUM a segmented sum of the dictionary's values over the group's ids, both on the device; one
+ * word per group and PERCENTILE (two per column for the sums) cross PCIe with the distinct counts.
+ *   fetch               h_values = the final double. h_values_i64 = the selected value of a PERCENTILE of an INT /
+ *                       LONG column (exact beyond 2^53), the integer sum of a DISTINCTSUM of an INT / LONG column
+ *                       when it fits int64, INT64_MIN otherwise
+ *   fetch_intermediate  (final value, 0); the histogram comes from fetch_value_counts
+ *   the server table    may order by any of them
+ * Of a GROUP BY column each is the key's own value.
+ *
  * DistinctCountAggregationFunction.extractGroupByResult: the value sets, CSR over the groups in fetch
  * order (after a server table: its kept groups, in its order). h_offsets[ngroups + 1];
  * h_values[h_offsets[g] .. h_offsets[g+1]) = group g's distinct values of aggregation agg_index, ascending
  * merged-dictionary id, each as fetch's key encoding (int64 / double bits / index for
  * pinot_amd_result_distinct_string). h_offsets may be NULL. h_values NULL: sizes only (h_num_values = the total).
- * More than cap values: EOVERFLOW. EINVAL when agg_index is not a DISTINCTCOUNT of the result.
+ * More than cap values: EOVERFLOW. EINVAL when agg_index is not a DISTINCTCOUNT, PERCENTILE, DISTINCTSUM or
+ * DISTINCTAVG of the result.
  * --------------------------------------------------------------------------------------------- */
 int pinot_amd_result_fetch_distinct_values(pinot_amd_result* r, int32_t agg_index, int64_t cap, int64_t* h_offsets,
                                            int64_t* h_values, int64_t* h_num_values);
-/* String value of merged-dictionary id `id` of aggregation agg_index's DISTINCTCOUNT column (NULL when it is
+/* The same CSR with h_counts[i] = the matching docs holding h_values[i]: each group's histogram, the
+ * intermediate result a server hands on for PERCENTILE (PercentileAggregationFunction's DoubleArrayList, sorted
+ * and run-length encoded). Same conventions (h_values NULL: sizes only; EOVERFLOW; after a server table its kept
+ * groups in its order); h_values without h_counts: EINVAL. Valid for all four value-set aggregation types; when
+ * no PERCENTILE of the column made the fold carry the doc counts, the first such call folds once more with them. */
+int pinot_amd_result_fetch_value_counts(pinot_amd_result* r, int32_t agg_index, int64_t cap, int64_t* h_offsets,
+                                        int64_t* h_values, int64_t* h_counts, int64_t* h_num_values);
+/* String value of merged-dictionary id `id` of aggregation agg_index's value-set column (NULL when it is
  * not a STRING column or id is out of range). */
 const char* pinot_amd_result_distinct_string(pinot_amd_result* r, int32_t agg_index, int64_t id);
 

@@ -14,6 +14,7 @@ constexpr int kMaxClauses = 16;                     // CNF clauses (4 bits each 
 constexpr int kMaxAcc = 16;                         // accumulator arrays (acc 0 = COUNT)
 constexpr int kMaxGroupCols = 16;
 constexpr int kMaxKeyWords = 8;                     // 64-bit words of a hash-table group key
+constexpr int kValueScanBlocks = 1024;              // blocks of the value-set fold's count scan at most
 // slack the kernels may read past the end of a column buffer (5 dwords of a bit window, a 32 B
 // value vector of the last tile, and up to 3 whole padding tiles of 8-byte values behind a segment's last
 // tile: the tile-level select walks steps of up to 4 tiles of one segment)

@@ -79,6 +79,13 @@ hipError_t launch_distinct_fold_count(const uint64_t* ckeys, int64_t nrows, cons
                                       unsigned long long* miss, hipStream_t st);
 hipError_t launch_distinct_fold_fill(const uint64_t* sorted, int64_t nrows, int cbits, const uint32_t* cnt, int64_t nbase,
                                      int64_t* off, int32_t* values, hipStream_t st);
+hipError_t launch_value_count_scan(const uint64_t* counts, int64_t n, int64_t* bsum, int64_t* cum, hipStream_t st);
+hipError_t launch_percentile_select(const int64_t* off, const int64_t* cum, const int32_t* values, int64_t ngroups,
+                                    const double* pct, int np, int32_t* out, hipStream_t st);
+int64_t distinct_fold_sum_tiles(int64_t nrows);
+hipError_t launch_distinct_fold_sum(const uint64_t* sorted, int64_t nrows, int cbits, const int64_t* off, int64_t nbase,
+                                    const double* dictd, const int64_t* dicti, double* sumd, uint64_t* sumi,
+                                    double* partd, uint64_t* parti, hipStream_t st);
 hipError_t launch_read_dict_ids(const uint8_t* packed, int bits, int64_t start, int64_t len, int32_t* out,
                                 hipStream_t st);
 hipError_t launch_pack_dict_ids(const int32_t* values, int64_t n, int bits, uint8_t* packed, hipStream_t st);
@@ -1292,7 +1299,12 @@ struct AggSpec {
   std::string column;   // empty for COUNT(*); first operand of an expression
   int32_t expr = 0;     // pinot_amd_expr_op (PINOT_AMD_EXPR_COLUMN: the column itself)
   std::string column2;  // second operand of an expression
+  double param = 0;     // PINOT_AMD_AGG_PERCENTILE: the percentile (part of no plan's identity: the fold reads it)
 };
+
+// the aggregations answered from a value-set query (execute_distinct): DISTINCTCOUNT, PERCENTILE, DISTINCTSUM,
+// DISTINCTAVG
+static bool is_value_set_agg(int32_t t) { return t >= PINOT_AMD_AGG_DISTINCTCOUNT && t <= PINOT_AMD_AGG_DISTINCTAVG; }
 
 struct MergedKeyColumn {
   int32_t type = 0;
@@ -1395,6 +1407,23 @@ int pinot_amd_query_add_aggregation(pinot_amd_query* q, int32_t agg_type, const 
     return fail(PINOT_AMD_EINVAL, "add_aggregation: bad type");
   AggSpec a{agg_type, (column && strcmp(column, "*") != 0) ? column : ""};
   if (agg_type != PINOT_AMD_AGG_COUNT && a.column.empty()) return fail(PINOT_AMD_EINVAL, "add_aggregation: column required");
+  if (out_index) *out_index = (int32_t)q->aggs.size();
+  q->aggs.push_back(a);
+  return 0;
+}
+
+int pinot_amd_query_add_aggregation_param(pinot_amd_query* q, int32_t agg_type, const char* column, double param,
+                                          int32_t* out_index) {
+  if (!q) return fail(PINOT_AMD_EINVAL, "add_aggregation_param: null query");
+  if (agg_type < PINOT_AMD_AGG_COUNT || agg_type > PINOT_AMD_AGG_DISTINCTAVG)
+    return fail(PINOT_AMD_EINVAL, "add_aggregation_param: bad type");
+  // AggregationFunctionFactory.java:534-536: 0 <= percentile <= 100 (NaN fails both comparisons)
+  if (agg_type == PINOT_AMD_AGG_PERCENTILE && !(param >= 0.0 && param <= 100.0))
+    return fail(PINOT_AMD_EINVAL, "add_aggregation_param: percentile %g not in [0, 100]", param);
+  AggSpec a{agg_type, (column && strcmp(column, "*") != 0) ? column : ""};
+  if (agg_type == PINOT_AMD_AGG_PERCENTILE) a.param = param;
+  if (agg_type != PINOT_AMD_AGG_COUNT && a.column.empty())
+    return fail(PINOT_AMD_EINVAL, "add_aggregation_param: column required");
   if (out_index) *out_index = (int32_t)q->aggs.size();
   q->aggs.push_back(a);
   return 0;
@@ -1570,8 +1599,24 @@ struct DistinctFold {
     std::vector<int64_t> h_off;
     std::vector<int32_t> h_vals;
     bool h_valid = false;
+    // the histogram's other uses. PERCENTILE (or a pinot_amd_result_fetch_value_counts): the value-set query's COUNT
+    // word exported (ccount), carried through the sort (scount: docs per sorted row) and scanned (cum); pct_aggs =
+    // the caller's PERCENTILE aggregations on this column, their percentiles on the device (pct), the selected
+    // value ids (pid: ng x pct_aggs). DISTINCTSUM / DISTINCTAVG: the merged dictionary on the device as doubles
+    // (and as int64 for INT / LONG: dicti), the per-group sums (sumd, sumi lo/hi) and the tiles' partials.
+    bool want_sum = false, has_counts = false;
+    std::vector<int32_t> pct_aggs;
+    std::vector<double> h_pct, h_dictd;
+    int sum_word = -1;  // first of the sum's two words in a group's host row (double bits, int64 or INT64_MIN)
+    DevBuf ccount, scount, cum, bsum, pct, pid, dictd, dicti, sumd, sumi, partd, parti;
+    std::vector<int64_t> h_cnts;  // scount on the host, with h_vals
+    bool h_cnts_valid = false;
   };
   std::deque<Child> children;
+  std::vector<AggSpec> aggs;       // the caller's aggregations
+  std::vector<int32_t> agg_word;   // per aggregation: its word in a group's host row beyond the counts, or -1
+  int nextra = 0;                  // those words
+  bool force_counts = false;       // a fetch_value_counts asked for the doc counts of every child
   std::vector<int32_t> base_agg_type, base_agg_acc, base_agg_acc2;  // the base's own, put back when this is dropped
   // per aggregation of the caller's query: -1 not a DISTINCTCOUNT, k >= 0 child k, -2 - j GROUP BY column j itself
   std::vector<int32_t> agg_child;
@@ -4888,11 +4933,13 @@ static int execute_distinct(pinot_amd_query* qq, pinot_amd_segment* const* segs_
     }
     safe = safe && std::all_of(seen.begin(), seen.end(), [](bool b) { return b; });
     if (safe && U.limit >= U.sort_agg_threshold && !U.server_final)
-      return fail(PINOT_AMD_EUNSUPPORTED, "DISTINCTCOUNT with a segment-level safe trim (ORDER BY = GROUP BY, LIMIT %lld "
+      return fail(PINOT_AMD_EUNSUPPORTED, "DISTINCTCOUNT / PERCENTILE / DISTINCTSUM / DISTINCTAVG with a segment-level safe "
+                                          "trim (ORDER BY = GROUP BY, LIMIT %lld "
                                           ">= sortAggregateLimitThreshold %lld)",
                   (long long)U.limit, (long long)U.sort_agg_threshold);
     if (!safe && U.min_seg_trim > 0)
-      return fail(PINOT_AMD_EUNSUPPORTED, "DISTINCTCOUNT with a segment-level trim (minSegmentGroupTrimSize %lld)",
+      return fail(PINOT_AMD_EUNSUPPORTED, "DISTINCTCOUNT / PERCENTILE / DISTINCTSUM / DISTINCTAVG with a segment-level trim "
+                                          "(minSegmentGroupTrimSize %lld)",
                   (long long)U.min_seg_trim);
   }
   pinot_amd_query base = U;
@@ -4909,11 +4956,17 @@ static int execute_distinct(pinot_amd_query* qq, pinot_amd_segment* const* segs_
   std::vector<std::string> child_cols;
   for (size_t a = 0; a < U.aggs.size(); ++a) {
     const AggSpec& A = U.aggs[a];
-    if (A.type != PINOT_AMD_AGG_DISTINCTCOUNT) {
+    if (!is_value_set_agg(A.type)) {
       base_index[a] = (int32_t)base.aggs.size();
       base.aggs.push_back(A);
       fold->agg_child.push_back(-1);
       continue;
+    }
+    if (A.type != PINOT_AMD_AGG_DISTINCTCOUNT) {  // PERCENTILE / DISTINCTSUM / DISTINCTAVG read the value as a number
+      if (!segs_in[0]) return fail(PINOT_AMD_EINVAL, "execute: null segment");
+      auto col = segs_in[0]->cols.find(A.column);  // (an unknown column fails in the value-set query's plan)
+      if (col != segs_in[0]->cols.end() && col->second->type == T_STRING)
+        return fail(PINOT_AMD_EINVAL, "aggregation %d over STRING column %s", A.type, A.column.c_str());
     }
     auto g = std::find(U.group_by.begin(), U.group_by.end(), A.column);
     if (g != U.group_by.end()) {  // the set of a group is its key's own value
@@ -4943,6 +4996,27 @@ static int execute_distinct(pinot_amd_query* qq, pinot_amd_segment* const* segs_
     DistinctFold::Child& C = fold->children.back();
     C.column = col;
     if (int rc = execute_impl(&cq, segs_in, n, stream, false, &C.r)) return rc;  // (fold's destructor frees the others)
+  }
+  // the words the fold appends to a group's host row after the children's distinct counts: per PERCENTILE the
+  // selected value's merged-dictionary id; per child with a DISTINCTSUM / DISTINCTAVG its sum (two words, shared);
+  // for a GROUP BY column the key's own id (its value is the percentile, the sum and the average)
+  fold->aggs = U.aggs;
+  fold->agg_word.assign(U.aggs.size(), -1);
+  for (size_t a = 0; a < U.aggs.size(); ++a) {
+    const int32_t t = U.aggs[a].type, k = fold->agg_child[a];
+    if (t != PINOT_AMD_AGG_PERCENTILE && t != PINOT_AMD_AGG_DISTINCTSUM && t != PINOT_AMD_AGG_DISTINCTAVG) continue;
+    if (k < 0 || t == PINOT_AMD_AGG_PERCENTILE) {
+      fold->agg_word[a] = fold->nextra++;
+      if (k >= 0) fold->children[(size_t)k].pct_aggs.push_back((int32_t)a);
+    } else {
+      DistinctFold::Child& C = fold->children[(size_t)k];
+      if (!C.want_sum) {
+        C.want_sum = true;
+        C.sum_word = fold->nextra;
+        fold->nextra += 2;
+      }
+      fold->agg_word[a] = C.sum_word;
+    }
   }
   // the caller's aggregation list and server table on the base's result: a DISTINCTCOUNT's final value is word
   // nacc + k of its group's host row (distinct_fold), or 1 for a GROUP BY column
@@ -4984,7 +5058,7 @@ static int execute_distinct(pinot_amd_query* qq, pinot_amd_segment* const* segs_
 int pinot_amd_execute(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, int32_t n, void* stream,
                       pinot_amd_result** out) {
   if (qq && std::any_of(qq->aggs.begin(), qq->aggs.end(),
-                        [](const AggSpec& a) { return a.type == PINOT_AMD_AGG_DISTINCTCOUNT; }))
+                        [](const AggSpec& a) { return is_value_set_agg(a.type); }))
     return no_throw("execute", [&] { return execute_distinct(qq, segs_in, n, stream, out); });
   return no_throw("execute", [&] { return execute_impl(qq, segs_in, n, stream, false, out); });
 }
@@ -5413,11 +5487,13 @@ static int compact_slots(pinot_amd_result* r, const GroupTable& T, hipStream_t s
 static int server_trim(pinot_amd_result* r);
 static int distinct_fold(pinot_amd_result* r, const uint64_t* d_hash_keys, int64_t ng);
 
-// words of a group's host row (cacc): its accumulators; a DISTINCTCOUNT result appends each value-set query's
-// distinct count and the group's index before the server table reorders the rows (the CSR's row)
+// words of a group's host row (cacc): its accumulators; a value-set result appends each value-set query's distinct
+// count, the words of its PERCENTILE / DISTINCTSUM / DISTINCTAVG aggregations (DistinctFold::agg_word) and the
+// group's index before the server table reorders the rows (the CSR's row)
 static int cacc_stride(const pinot_amd_result* r) {
-  return std::max(r->q.nacc, 1) + (r->dc ? (int)r->dc->children.size() + 1 : 0);
+  return std::max(r->q.nacc, 1) + (r->dc ? (int)r->dc->children.size() + r->dc->nextra + 1 : 0);
 }
+static const MergedKeyColumn* distinct_dictionary(const pinot_amd_result* r, int32_t agg_index);
 
 static int compact_groups(pinot_amd_result* r) {
   if (r->dc && r->dc->children.size())  // a failed self-check of a value-set query voids every read
@@ -5526,6 +5602,39 @@ static void final_value(const pinot_amd_result* r, const uint64_t* A, int a, dou
     // the set's size: the fold's count in the group's row, or 1 for a GROUP BY column (its key's own value)
     *vi_out = r->agg_acc[a] < 0 ? 1 : (int64_t)A[r->agg_acc[a]];
     *v_out = (double)*vi_out;
+    return;
+  }
+  if (is_value_set_agg(r->agg_type[a])) {
+    // the fold's words in the group's row (distinct_fold). PERCENTILE: the selected value's id in the column's
+    // merged dictionary (-1: no doc, PercentileAggregationFunction's DEFAULT_FINAL_RESULT); DISTINCTSUM /
+    // DISTINCTAVG: the sum as double and as int64, over the distinct count; of a GROUP BY column: the key's value
+    const DistinctFold& D = *r->dc;
+    const int32_t k = D.agg_child[(size_t)a];
+    const uint64_t* X = A + std::max(r->q.nacc, 1) + (int)D.children.size() + D.agg_word[(size_t)a];
+    double v;
+    int64_t vi = INT64_MIN;
+    if (r->agg_type[a] == PINOT_AMD_AGG_PERCENTILE || k < 0) {
+      const int64_t id = (int64_t)X[0];
+      const MergedKeyColumn* m = distinct_dictionary(r, a);
+      if (id < 0 || !m) {
+        v = -INFINITY;
+      } else if (is_float(m->type)) {
+        v = m->vd[(size_t)id];
+      } else {
+        vi = m->vi[(size_t)id];
+        v = (double)vi;
+      }
+      if (r->agg_type[a] == PINOT_AMD_AGG_DISTINCTAVG) vi = INT64_MIN;
+    } else {
+      memcpy(&v, &X[0], 8);
+      vi = (int64_t)X[1];
+      if (r->agg_type[a] == PINOT_AMD_AGG_DISTINCTAVG) {  // DistinctAvgAggregationFunction: sum / size, 0.0 / 0 = NaN
+        v = v / (double)(int64_t)A[r->agg_acc[a]];
+        vi = INT64_MIN;
+      }
+    }
+    *v_out = v;
+    *vi_out = vi;
     return;
   }
   const int acc = r->agg_acc[a];
@@ -5968,10 +6077,17 @@ static int distinct_fold(pinot_amd_result* r, const uint64_t* d_hash_keys, int64
   }
   std::vector<std::vector<uint32_t>> hcnt((size_t)nch);
   std::vector<unsigned long long> hmiss((size_t)nch, 0);
+  std::vector<std::vector<int32_t>> hpid((size_t)nch);
+  std::vector<std::vector<double>> hsumd((size_t)nch);
+  std::vector<std::vector<uint64_t>> hsumi((size_t)nch);
   for (int k = 0; k < nch; ++k) {
     DistinctFold::Child& C = D.children[(size_t)k];
     pinot_amd_result* c = C.r;
     C.h_valid = false;
+    // a DISTINCTCOUNT-only child runs what it always ran: the doc counts ride along only for a PERCENTILE (or a
+    // pinot_amd_result_fetch_value_counts), the dictionary and the sums only for a DISTINCTSUM / DISTINCTAVG
+    const int np = (int)C.pct_aggs.size();
+    const bool counts = np > 0 || D.force_counts;
     if (int rc = check_overflow(c)) return rc;  // (the child's self-check too)
     const GroupTable T = group_table(c);
     int64_t nrows = 0;
@@ -5993,19 +6109,70 @@ static int distinct_fold(pinot_amd_result* r, const uint64_t* d_hash_keys, int64
       if (int rc = C.sorted.ensure((size_t)nrows * 8)) return rc;
       if (int rc = C.scratch.ensure(sort_rows_scratch(nrows))) return rc;
       if (int rc = C.vals.ensure((size_t)nrows * 4)) return rc;
-      HIP_OK(launch_export_groups((const int32_t*)c->c_idx.p, nrows, T.keys, T.slots, T.acc, 0, kc, (uint64_t*)C.ckeys.p,
-                                  nullptr, st));
+      if (counts) {
+        if (int rc = C.ccount.ensure((size_t)nrows * 8)) return rc;
+        if (int rc = C.scount.ensure((size_t)nrows * 8)) return rc;
+        if (int rc = C.cum.ensure((size_t)nrows * 8)) return rc;
+        if (int rc = C.bsum.ensure((size_t)kValueScanBlocks * 8)) return rc;
+      }
+      // (the value-set query's only accumulator is its COUNT: the docs holding the row's value)
+      HIP_OK(launch_export_groups((const int32_t*)c->c_idx.p, nrows, T.keys, T.slots, T.acc, counts ? 1 : 0, kc,
+                                  (uint64_t*)C.ckeys.p, counts ? (uint64_t*)C.ccount.p : nullptr, st));
     }
     HIP_OK(launch_distinct_fold_count((const uint64_t*)C.ckeys.p, nrows, kc, kb, bkeys, ng, C.cbits, (uint32_t*)C.cnt.p,
                                       (uint64_t*)C.pair.p, (unsigned long long*)C.miss.p, st));
     const int pair_bits = C.cbits + bits_for(ng + 1);  // group indices 0 .. ng (ng: no base group)
-    HIP_OK(sort_rows_by_key((const uint64_t*)C.pair.p, 1, &pair_bits, nullptr, 0, nrows, C.scratch.p, (uint64_t*)C.sorted.p,
-                            nullptr, st));
+    HIP_OK(sort_rows_by_key((const uint64_t*)C.pair.p, 1, &pair_bits, counts ? (const uint64_t*)C.ccount.p : nullptr,
+                            counts ? 1 : 0, nrows, C.scratch.p, (uint64_t*)C.sorted.p,
+                            counts ? (uint64_t*)C.scount.p : nullptr, st));
     HIP_OK(launch_distinct_fold_fill((const uint64_t*)C.sorted.p, nrows, C.cbits, (const uint32_t*)C.cnt.p, ng,
                                      (int64_t*)C.off.p, (int32_t*)C.vals.p, st));
     hcnt[(size_t)k].assign((size_t)ng, 0);
     if (ng > 0) HIP_OK(hipMemcpyAsync(hcnt[(size_t)k].data(), C.cnt.p, (size_t)ng * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(&hmiss[(size_t)k], C.miss.p, 8, hipMemcpyDeviceToHost, st));
+    C.has_counts = counts;
+    C.h_cnts_valid = false;
+    const MergedKeyColumn& m = *c->keys.back();
+    if (counts) HIP_OK(launch_value_count_scan((const uint64_t*)C.scount.p, nrows, (int64_t*)C.bsum.p, (int64_t*)C.cum.p, st));
+    if (np > 0 && ng > 0) {  // rank selection: ng x np value ids
+      C.h_pct.clear();
+      for (int32_t a : C.pct_aggs) C.h_pct.push_back(D.aggs[(size_t)a].param);
+      if (int rc = C.pct.ensure((size_t)np * 8)) return rc;
+      if (int rc = C.pid.ensure((size_t)ng * np * 4)) return rc;
+      HIP_OK(hipMemcpyAsync(C.pct.p, C.h_pct.data(), (size_t)np * 8, hipMemcpyHostToDevice, st));
+      HIP_OK(launch_percentile_select((const int64_t*)C.off.p, (const int64_t*)C.cum.p, (const int32_t*)C.vals.p, ng,
+                                      (const double*)C.pct.p, np, (int32_t*)C.pid.p, st));
+      hpid[(size_t)k].assign((size_t)ng * np, -1);
+      HIP_OK(hipMemcpyAsync(hpid[(size_t)k].data(), C.pid.p, (size_t)ng * np * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (C.want_sum && ng > 0) {  // the column's merged dictionary, uploaded once per fold, and the segmented sums
+      if (m.type == T_STRING) return fail(PINOT_AMD_EINVAL, "DISTINCTSUM(%s): a STRING column", C.column.c_str());
+      const bool integer = !is_float(m.type);
+      const size_t card = std::max<size_t>(m.size(), 1);
+      if (integer) {
+        C.h_dictd.resize(m.vi.size());
+        for (size_t i = 0; i < m.vi.size(); ++i) C.h_dictd[i] = (double)m.vi[i];
+      }
+      const std::vector<double>& dd = integer ? C.h_dictd : m.vd;
+      if (int rc = C.dictd.ensure(card * 8)) return rc;
+      if (!dd.empty()) HIP_OK(hipMemcpyAsync(C.dictd.p, dd.data(), dd.size() * 8, hipMemcpyHostToDevice, st));
+      if (integer) {
+        if (int rc = C.dicti.ensure(card * 8)) return rc;
+        if (!m.vi.empty()) HIP_OK(hipMemcpyAsync(C.dicti.p, m.vi.data(), m.vi.size() * 8, hipMemcpyHostToDevice, st));
+      }
+      const size_t tiles = (size_t)std::max<int64_t>(distinct_fold_sum_tiles(nrows), 1);
+      if (int rc = C.sumd.ensure((size_t)ng * 8)) return rc;
+      if (int rc = C.sumi.ensure((size_t)ng * 16)) return rc;
+      if (int rc = C.partd.ensure(tiles * 2 * 8)) return rc;
+      if (int rc = C.parti.ensure(tiles * 4 * 8)) return rc;
+      HIP_OK(launch_distinct_fold_sum((const uint64_t*)C.sorted.p, nrows, C.cbits, (const int64_t*)C.off.p, ng,
+                                      (const double*)C.dictd.p, integer ? (const int64_t*)C.dicti.p : nullptr,
+                                      (double*)C.sumd.p, (uint64_t*)C.sumi.p, (double*)C.partd.p, (uint64_t*)C.parti.p, st));
+      hsumd[(size_t)k].assign((size_t)ng, 0.0);
+      hsumi[(size_t)k].assign((size_t)ng * 2, 0);
+      HIP_OK(hipMemcpyAsync(hsumd[(size_t)k].data(), C.sumd.p, (size_t)ng * 8, hipMemcpyDeviceToHost, st));
+      if (integer) HIP_OK(hipMemcpyAsync(hsumi[(size_t)k].data(), C.sumi.p, (size_t)ng * 16, hipMemcpyDeviceToHost, st));
+    }
   }
   HIP_OK(hipStreamSynchronize(st));
   // a child row without a base group: a group the base did not admit under numGroupsLimit (its values are dropped
@@ -6020,6 +6187,38 @@ static int distinct_fold(pinot_amd_result* r, const uint64_t* d_hash_keys, int64
     for (int k = 0; k < nch; ++k) rows[(size_t)g * S + nacc + k] = hcnt[(size_t)k][(size_t)g];
     rows[(size_t)g * S + S - 1] = (uint64_t)g;
   }
+  // the PERCENTILE / DISTINCTSUM / DISTINCTAVG words (DistinctFold::agg_word), read by final_value
+  for (int k = 0; k < nch; ++k) {
+    const DistinctFold::Child& C = D.children[(size_t)k];
+    const int np = (int)C.pct_aggs.size();
+    for (int j = 0; j < np; ++j) {
+      const int w = nacc + nch + D.agg_word[(size_t)C.pct_aggs[(size_t)j]];
+      for (int64_t g = 0; g < ng; ++g) rows[(size_t)g * S + w] = (uint64_t)(int64_t)hpid[(size_t)k][(size_t)g * np + j];
+    }
+    if (!C.want_sum) continue;
+    const bool integer = !is_float(C.r->keys.back()->type);
+    const int w = nacc + nch + C.sum_word;
+    for (int64_t g = 0; g < ng; ++g) {
+      // DistinctSumAggregationFunction starts from 0.0 (a set of -0.0 alone sums to 0.0); an INT / LONG column's
+      // sum is the exact integer, rounded once, whenever it fits int64
+      double d = 0.0 + hsumd[(size_t)k][(size_t)g];
+      int64_t vi = INT64_MIN;
+      if (integer) {
+        const uint64_t lo = hsumi[(size_t)k][(size_t)g * 2];
+        const int64_t hi = (int64_t)hsumi[(size_t)k][(size_t)g * 2 + 1];
+        if (hi == ((int64_t)lo >> 63) && (int64_t)lo != INT64_MIN) {
+          vi = (int64_t)lo;
+          d = (double)vi;
+        }
+      }
+      memcpy(&rows[(size_t)g * S + w], &d, 8);
+      rows[(size_t)g * S + w + 1] = (uint64_t)vi;
+    }
+  }
+  for (size_t a = 0; a < D.aggs.size(); ++a)  // of a GROUP BY column: the key's own id (before the server table)
+    if (D.agg_child[a] <= -2 && D.agg_word[a] >= 0)
+      for (int64_t g = 0; g < ng; ++g)
+        rows[(size_t)g * S + nacc + nch + D.agg_word[a]] = (uint64_t)group_key_id(r, g, -2 - D.agg_child[a]);
   r->cacc.swap(rows);
   return 0;
 }
@@ -6027,7 +6226,7 @@ static int distinct_fold(pinot_amd_result* r, const uint64_t* d_hash_keys, int64
 }  // extern "C"
 
 // the merged dictionary of aggregation agg_index's DISTINCTCOUNT column, or null
-static const MergedKeyColumn* distinct_dictionary(pinot_amd_result* r, int32_t agg_index) {
+static const MergedKeyColumn* distinct_dictionary(const pinot_amd_result* r, int32_t agg_index) {
   if (!r || !r->dc || agg_index < 0 || agg_index >= (int32_t)r->dc->agg_child.size()) return nullptr;
   const int32_t k = r->dc->agg_child[(size_t)agg_index];
   if (k == -1) return nullptr;
@@ -6035,16 +6234,25 @@ static const MergedKeyColumn* distinct_dictionary(pinot_amd_result* r, int32_t a
   return r->keys[(size_t)(-2 - k)].get();
 }
 
-int pinot_amd_result_fetch_distinct_values(pinot_amd_result* r, int32_t agg_index, int64_t cap, int64_t* h_offsets,
-                                           int64_t* h_values, int64_t* h_num_values) {
-  if (!r || cap < 0 || !h_num_values) return fail(PINOT_AMD_EINVAL, "fetch_distinct_values: bad arguments");
+// pinot_amd_result_fetch_distinct_values (with_counts false) and pinot_amd_result_fetch_value_counts: the groups'
+// values as CSR, and each value's matching docs
+static int fetch_value_csr(const char* what, bool with_counts, pinot_amd_result* r, int32_t agg_index, int64_t cap,
+                           int64_t* h_offsets, int64_t* h_values, int64_t* h_counts, int64_t* h_num_values) {
+  if (!r || cap < 0 || !h_num_values) return fail(PINOT_AMD_EINVAL, "%s: bad arguments", what);
   const MergedKeyColumn* m = distinct_dictionary(r, agg_index);
-  if (!m) return fail(PINOT_AMD_EINVAL, "fetch_distinct_values: aggregation %d is not a DISTINCTCOUNT of this result", agg_index);
-  return no_throw("fetch_distinct_values", [&]() -> int {
-    if (int rc = compact_groups(r)) return rc;
+  if (!m) return fail(PINOT_AMD_EINVAL, "%s: aggregation %d is not a value-set aggregation of this result", what, agg_index);
+  return no_throw(what, [&]() -> int {
     DistinctFold& D = *r->dc;
     const int32_t k = D.agg_child[(size_t)agg_index];
+    if (int rc = compact_groups(r)) return rc;
+    if (with_counts && h_values && k >= 0 && !D.children[(size_t)k].has_counts) {
+      // no PERCENTILE asked for the doc counts: fold again, carrying them (and in later executions of this result)
+      D.force_counts = true;
+      r->compacted = false;
+      if (int rc = compact_groups(r)) return rc;
+    }
     const int S = cacc_stride(r);
+    const int nacc = std::max(r->q.nacc, 1);
     const int64_t ng = r->ngroups;
     auto encode = [&](int64_t id) -> int64_t {
       int64_t o;
@@ -6056,15 +6264,18 @@ int pinot_amd_result_fetch_distinct_values(pinot_amd_result* r, int32_t agg_inde
     int64_t total = 0;
     for (int64_t g = 0; g < ng; ++g) {
       if (h_offsets) h_offsets[g] = total;
-      total += k >= 0 ? (int64_t)r->cacc[(size_t)g * S + (S - 1 - (int)D.children.size()) + k] : 1;
+      total += k >= 0 ? (int64_t)r->cacc[(size_t)g * S + nacc + k] : 1;
     }
     if (h_offsets) h_offsets[ng] = total;
     *h_num_values = total;
     if (!h_values) return 0;  // sizing call
     if (total > cap)
-      return fail(PINOT_AMD_EOVERFLOW, "fetch_distinct_values: %lld values exceed capacity %lld", (long long)total, (long long)cap);
-    if (k < 0) {  // a GROUP BY column: each group's set is its key's value
-      for (int64_t g = 0; g < ng; ++g) h_values[g] = encode(group_key_id(r, g, -2 - k));
+      return fail(PINOT_AMD_EOVERFLOW, "%s: %lld values exceed capacity %lld", what, (long long)total, (long long)cap);
+    if (k < 0) {  // a GROUP BY column: each group's set is its key's value, held by every doc of the group
+      for (int64_t g = 0; g < ng; ++g) {
+        h_values[g] = encode(group_key_id(r, g, -2 - k));
+        if (with_counts) h_counts[g] = (int64_t)r->cacc[(size_t)g * S];
+      }
       return 0;
     }
     DistinctFold::Child& C = D.children[(size_t)k];
@@ -6081,13 +6292,35 @@ int pinot_amd_result_fetch_distinct_values(pinot_amd_result* r, int32_t agg_inde
       }
       C.h_valid = true;
     }
+    if (with_counts && !C.h_cnts_valid) {  // the docs per sorted row, the CSR's entries first
+      C.h_cnts.assign(C.h_vals.size(), 0);
+      if (!C.h_cnts.empty()) {
+        HIP_OK(hipMemcpyAsync(C.h_cnts.data(), C.scount.p, C.h_cnts.size() * 8, hipMemcpyDeviceToHost, r->stream));
+        HIP_OK(hipStreamSynchronize(r->stream));
+      }
+      C.h_cnts_valid = true;
+    }
     int64_t o = 0;
     for (int64_t g = 0; g < ng; ++g) {  // the rows the server table kept, in its order
       const int64_t src = (int64_t)r->cacc[(size_t)g * S + S - 1];
-      for (int64_t i = C.h_off[(size_t)src]; i < C.h_off[(size_t)src + 1]; ++i) h_values[o++] = encode(C.h_vals[(size_t)i]);
+      for (int64_t i = C.h_off[(size_t)src]; i < C.h_off[(size_t)src + 1]; ++i) {
+        if (with_counts) h_counts[o] = C.h_cnts[(size_t)i];
+        h_values[o++] = encode(C.h_vals[(size_t)i]);
+      }
     }
     return 0;
   });
+}
+
+int pinot_amd_result_fetch_distinct_values(pinot_amd_result* r, int32_t agg_index, int64_t cap, int64_t* h_offsets,
+                                           int64_t* h_values, int64_t* h_num_values) {
+  return fetch_value_csr("fetch_distinct_values", false, r, agg_index, cap, h_offsets, h_values, nullptr, h_num_values);
+}
+
+int pinot_amd_result_fetch_value_counts(pinot_amd_result* r, int32_t agg_index, int64_t cap, int64_t* h_offsets,
+                                        int64_t* h_values, int64_t* h_counts, int64_t* h_num_values) {
+  if (h_values && !h_counts) return fail(PINOT_AMD_EINVAL, "fetch_value_counts: values without counts");
+  return fetch_value_csr("fetch_value_counts", true, r, agg_index, cap, h_offsets, h_values, h_counts, h_num_values);
 }
 
 const char* pinot_amd_result_distinct_string(pinot_amd_result* r, int32_t agg_index, int64_t id) {

@@ -892,6 +892,18 @@ __global__ void export_groups_kernel(const int32_t* slots, int64_t ngroups, cons
   }
 }
 
+// device pointers as global-address-space pointers: loads through the generic ones compiled to flat loads, which
+// also count against lgkmcnt -- every wait for LDS traffic (the inverted-index expansion's atomics, the value-set
+// fold's LDS scans) then waited for them
+template <class T>
+__device__ __forceinline__ const __attribute__((address_space(1))) T* gptr(const T* p) {
+  return (const __attribute__((address_space(1))) T*)p;
+}
+template <class T>
+__device__ __forceinline__ __attribute__((address_space(1))) T* gout(T* p) {
+  return (__attribute__((address_space(1))) T*)p;
+}
+
 // DISTINCTCOUNT fold (DistinctCountAggregationFunction's per-group dictId sets, built from two results): the
 // child result's groups are (g..., c) rows, the base result's groups are the query's. Per child row: the column
 // ids decoded with the child's packing, the g prefix packed again as the base packs it, and the base group b
@@ -947,6 +959,228 @@ __global__ void __launch_bounds__(kBlock) distinct_fold_fill_kernel(const uint64
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nrows; i += (int64_t)gridDim.x * blockDim.x) {
     const uint64_t p = sorted[i];
     if ((int64_t)(p >> cbits) < nbase) values[i] = (int32_t)(p & ((1ull << cbits) - 1ull));
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Value-set fold, the histogram's other uses (PERCENTILE, DISTINCTSUM, DISTINCTAVG). The sorted pair rows are each
+// group's distinct values in merged-dictionary order; with the value-set query's COUNT word carried through the
+// sort as payload, row i also has the number of matching docs holding that value: the group's histogram.
+// ------------------------------------------------------------------------------------------------
+// Inclusive scan of x over the block's threads on top of *carry (LDS), which moves past them. Every thread calls.
+__device__ __forceinline__ int64_t block_scan_step_i64(int64_t x, int64_t* wtot, int64_t* carry) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int64_t incl = x;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int64_t y = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += y;
+  }
+  if (lane == 63) wtot[wave] = incl;
+  __syncthreads();
+  int64_t out = *carry + incl;
+  for (int w = 0; w < wave; ++w) out += wtot[w];
+  __syncthreads();
+  if (threadIdx.x == kBlock - 1) *carry = out;
+  __syncthreads();
+  return out;
+}
+
+// (a) device-wide inclusive scan of the sorted rows' 64-bit doc counts, two launches: block b owns the rows
+// [b * span, (b + 1) * span) (span a multiple of kBlock); the first kernel totals each span, the second scans its
+// span on top of the totals of the spans before it.
+__global__ void __launch_bounds__(kBlock) value_count_span_kernel(const uint64_t* counts, int64_t n, int64_t span,
+                                                                  int64_t* bsum) {
+  __shared__ int64_t wtot[kBlock / 64];
+  const int64_t lo = (int64_t)blockIdx.x * span, hi = lo + span < n ? lo + span : n;
+  int64_t s = 0;
+  for (int64_t i = lo + threadIdx.x; i < hi; i += kBlock) s += (int64_t)gptr(counts)[i];
+  s = wave_sum_i64(s);
+  if ((threadIdx.x & 63) == 0) wtot[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int64_t t = 0;
+    for (int w = 0; w < kBlock / 64; ++w) t += wtot[w];
+    gout(bsum)[blockIdx.x] = t;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) value_count_scan_kernel(const uint64_t* counts, int64_t n, int64_t span,
+                                                                  const int64_t* bsum, int64_t* cum) {
+  __shared__ int64_t wtot[kBlock / 64];
+  __shared__ int64_t carry;
+  int64_t s = 0;
+  for (int b = threadIdx.x; b < (int)blockIdx.x; b += kBlock) s += gptr(bsum)[b];
+  s = wave_sum_i64(s);
+  if ((threadIdx.x & 63) == 0) wtot[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int64_t t = 0;
+    for (int w = 0; w < kBlock / 64; ++w) t += wtot[w];
+    carry = t;
+  }
+  __syncthreads();
+  const int64_t lo = (int64_t)blockIdx.x * span, hi = lo + span < n ? lo + span : n;
+  for (int64_t base = lo; base < hi; base += kBlock) {
+    const int64_t i = base + threadIdx.x;
+    const int64_t incl = block_scan_step_i64(i < hi ? (int64_t)gptr(counts)[i] : 0, wtot, &carry);
+    if (i < hi) gout(cum)[i] = incl;
+  }
+}
+
+// (b) rank selection (PercentileAggregationFunction.extractFinalResult over the group's sorted values: the last
+// one for p = 100, else the element at (int) ((double) n * p / 100.0)). One thread per (group, percentile): the
+// group's slice [off[g], off[g + 1]) of the cumulative counts, minus the count before the slice, is the number of
+// docs up to each value; the first value whose cumulative count exceeds the target index holds that doc.
+// out[g * np + j] = its merged-dictionary id, -1 for a group without values.
+__global__ void __launch_bounds__(kBlock) percentile_select_kernel(const int64_t* off, const int64_t* cum,
+                                                                   const int32_t* values, int64_t ngroups,
+                                                                   const double* pct, int np, int32_t* out) {
+  const int64_t total = ngroups * np;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t g = i / np;
+    const int j = (int)(i - g * np);
+    const int64_t lo = gptr(off)[g], hi = gptr(off)[g + 1];
+    int32_t id = -1;
+    if (hi > lo) {
+      const int64_t before = lo > 0 ? gptr(cum)[lo - 1] : 0;
+      const int64_t n = gptr(cum)[hi - 1] - before;
+      const double p = gptr(pct)[j];
+      int64_t t = p == 100.0 ? n - 1 : (int64_t)((double)n * p / 100.0);
+      if (t > n - 1) t = n - 1;  // (a product rounded up to n: Java would index past the array)
+      if (t < 0) t = 0;
+      int64_t a = lo, b = hi - 1;  // the first row of the slice with cum - before > t (the last row always has)
+      while (a < b) {
+        const int64_t mid = a + ((b - a) >> 1);
+        if (gptr(cum)[mid] - before > t) b = mid;
+        else a = mid + 1;
+      }
+      id = gptr(values)[a];
+    }
+    gout(out)[i] = id;
+  }
+}
+
+// (c) segmented sum of the groups' dictionary values (DistinctSumAggregationFunction: the sum of the set as
+// doubles), in a fixed order so that two executions return the same bits. Two levels over tiles of kBlock rows,
+// whatever the groups' sizes: a tile's threads take one row each and run a segmented Hillis-Steele scan in LDS
+// (a row adds the row d before it while both are of one group); the last row of each run then holds the run's sum.
+// A run that is its whole group is final (sumd / sumi); a run cut by the tile's edge is a partial: slot 0 of the
+// tile when the group began before the tile, slot 1 when it begins inside and goes on. The second kernel folds
+// the partials of each group that spans tiles, tile order, with a block tree. dicti (INT / LONG columns, else
+// null) is summed exactly in 128 bits (lo, hi words).
+__global__ void __launch_bounds__(kBlock) distinct_fold_sum_tile_kernel(const uint64_t* sorted, int cbits,
+                                                                        const int64_t* off, int64_t nbase,
+                                                                        const double* dictd, const int64_t* dicti,
+                                                                        double* sumd, uint64_t* sumi, double* partd,
+                                                                        uint64_t* parti) {
+  __shared__ double sd[kBlock];
+  __shared__ uint64_t slo[kBlock];
+  __shared__ int64_t shi[kBlock];
+  __shared__ int64_t sg[kBlock];
+  const int t = threadIdx.x;
+  const int64_t nvalid = gptr(off)[nbase];  // rows with a base group (the others sorted behind them)
+  const int64_t ntiles = (nvalid + kBlock - 1) / kBlock;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t r = tile * kBlock + t;
+    int64_t g = -1;
+    double d = 0.0;
+    uint64_t lo = 0;
+    int64_t hi = 0;
+    if (r < nvalid) {
+      const uint64_t p = gptr(sorted)[r];
+      const int64_t id = (int64_t)(p & ((1ull << cbits) - 1ull));
+      g = (int64_t)(p >> cbits);
+      d = gptr(dictd)[id];
+      if (dicti) {
+        const int64_t x = gptr(dicti)[id];
+        lo = (uint64_t)x;
+        hi = x < 0 ? -1 : 0;
+      }
+    }
+    sg[t] = g;
+    sd[t] = d;
+    slo[t] = lo;
+    shi[t] = hi;
+    __syncthreads();
+#pragma unroll
+    for (int o = 1; o < kBlock; o <<= 1) {
+      const bool add = t >= o && sg[t - o] == g;
+      const double nd = add ? sd[t - o] : 0.0;
+      const uint64_t nlo = add ? slo[t - o] : 0ull;
+      const int64_t nhi = add ? shi[t - o] : 0;
+      __syncthreads();
+      if (add) {
+        d = nd + d;  // the earlier rows' sum first: one fixed tree per run
+        const uint64_t l2 = lo + nlo;
+        hi = hi + nhi + (l2 < lo ? 1 : 0);
+        lo = l2;
+        sd[t] = d;
+        slo[t] = lo;
+        shi[t] = hi;
+      }
+      __syncthreads();
+    }
+    if (r < nvalid && (t == kBlock - 1 || r == nvalid - 1 || sg[t + 1] != g)) {  // the last row of a run
+      const int64_t g0 = gptr(off)[g], g1 = gptr(off)[g + 1];
+      const int64_t tile0 = tile * kBlock;
+      if (g0 >= tile0 && g1 <= tile0 + kBlock) {
+        gout(sumd)[g] = d;
+        gout(sumi)[2 * g] = lo;
+        gout(sumi)[2 * g + 1] = (uint64_t)hi;
+      } else {
+        const int64_t s = tile * 2 + (g0 < tile0 ? 0 : 1);
+        gout(partd)[s] = d;
+        gout(parti)[2 * s] = lo;
+        gout(parti)[2 * s + 1] = (uint64_t)hi;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) distinct_fold_sum_span_kernel(const int64_t* off, int64_t nbase,
+                                                                        const double* partd, const uint64_t* parti,
+                                                                        double* sumd, uint64_t* sumi) {
+  __shared__ double sd[kBlock];
+  __shared__ uint64_t slo[kBlock];
+  __shared__ int64_t shi[kBlock];
+  const int t = threadIdx.x;
+  for (int64_t g = blockIdx.x; g < nbase; g += gridDim.x) {
+    const int64_t g0 = gptr(off)[g], g1 = gptr(off)[g + 1];
+    if (g1 <= g0) continue;
+    const int64_t t0 = g0 / kBlock, t1 = (g1 - 1) / kBlock;
+    if (t0 == t1) continue;  // within one tile: final already
+    double d = 0.0;
+    uint64_t lo = 0;
+    int64_t hi = 0;
+    for (int64_t k = t0 + t; k <= t1; k += kBlock) {  // (partials of tiles, not rows: tiles k, k + kBlock, ...)
+      const int64_t s = k * 2 + (g0 < k * kBlock ? 0 : 1);
+      d += gptr(partd)[s];
+      const uint64_t plo = gptr(parti)[2 * s];
+      const uint64_t l2 = lo + plo;
+      hi = hi + (int64_t)gptr(parti)[2 * s + 1] + (l2 < lo ? 1 : 0);
+      lo = l2;
+    }
+    sd[t] = d;
+    slo[t] = lo;
+    shi[t] = hi;
+    __syncthreads();
+    for (int o = kBlock / 2; o > 0; o >>= 1) {
+      if (t < o) {
+        sd[t] = sd[t] + sd[t + o];
+        const uint64_t l2 = slo[t] + slo[t + o];
+        shi[t] = shi[t] + shi[t + o] + (l2 < slo[t] ? 1 : 0);
+        slo[t] = l2;
+      }
+      __syncthreads();
+    }
+    if (t == 0) {
+      gout(sumd)[g] = sd[0];
+      gout(sumi)[2 * g] = slo[0];
+      gout(sumi)[2 * g + 1] = (uint64_t)shi[0];
+    }
+    __syncthreads();
   }
 }
 
@@ -1239,13 +1473,6 @@ struct RoaringContainer {
   uint32_t pad;
   uint64_t offset;   // byte offset of the container payload inside the staged inverted index
 };
-
-// a job's device pointers as global-address-space pointers: loads through the generic ones compiled to flat
-// loads, which also count against lgkmcnt -- every wait for the expansion's LDS atomics then waited for them
-template <class T>
-__device__ __forceinline__ const __attribute__((address_space(1))) T* gptr(const T* p) {
-  return (const __attribute__((address_space(1))) T*)p;
-}
 
 // descriptor of the container at position ci of a job's selection
 __device__ __forceinline__ RoaringContainer expand_desc(const ExpandJob& J, int32_t ci) {
@@ -2220,6 +2447,43 @@ hipError_t launch_distinct_fold_fill(const uint64_t* sorted, int64_t nrows, int 
   if (nrows > 0)
     hipLaunchKernelGGL(distinct_fold_fill_kernel, dim3(grid_cap(nrows, kBlock, 8192)), dim3(kBlock), 0, st, sorted, nrows,
                        cbits, nbase, values);
+  return hipGetLastError();
+}
+
+// value-set fold (a): cum[i] = counts[0] + ... + counts[i] over the n sorted rows; bsum: kValueScanBlocks words
+hipError_t launch_value_count_scan(const uint64_t* counts, int64_t n, int64_t* bsum, int64_t* cum, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  const int64_t nblk = std::min<int64_t>(kValueScanBlocks, (n + kBlock - 1) / kBlock);
+  const int64_t span = ((n + nblk - 1) / nblk + kBlock - 1) / kBlock * kBlock;
+  hipLaunchKernelGGL(value_count_span_kernel, dim3((unsigned)nblk), dim3(kBlock), 0, st, counts, n, span, bsum);
+  hipLaunchKernelGGL(value_count_scan_kernel, dim3((unsigned)nblk), dim3(kBlock), 0, st, counts, n, span,
+                     (const int64_t*)bsum, cum);
+  return hipGetLastError();
+}
+
+// value-set fold (b): out[g * np + j] = the value id at percentile pct[j] of group g (-1: no values)
+hipError_t launch_percentile_select(const int64_t* off, const int64_t* cum, const int32_t* values, int64_t ngroups,
+                                    const double* pct, int np, int32_t* out, hipStream_t st) {
+  if (ngroups <= 0 || np <= 0) return hipSuccess;
+  hipLaunchKernelGGL(percentile_select_kernel, dim3(grid_cap(ngroups * np, kBlock, 8192)), dim3(kBlock), 0, st, off, cum,
+                     values, ngroups, pct, np, out);
+  return hipGetLastError();
+}
+
+// value-set fold (c): sumd[g] / sumi[2g, 2g + 1] = the sum of group g's distinct values (zeroed here: a group
+// without values sums to 0). partd / parti: 2 / 4 words per tile of kBlock rows (distinct_fold_sum_tiles).
+int64_t distinct_fold_sum_tiles(int64_t nrows) { return (nrows + kBlock - 1) / kBlock; }
+hipError_t launch_distinct_fold_sum(const uint64_t* sorted, int64_t nrows, int cbits, const int64_t* off, int64_t nbase,
+                                    const double* dictd, const int64_t* dicti, double* sumd, uint64_t* sumi,
+                                    double* partd, uint64_t* parti, hipStream_t st) {
+  if (nbase <= 0) return hipSuccess;
+  hipError_t e = hipMemsetAsync(sumd, 0, (size_t)nbase * 8, st);
+  if (e == hipSuccess) e = hipMemsetAsync(sumi, 0, (size_t)nbase * 16, st);
+  if (e != hipSuccess || nrows <= 0) return e;
+  hipLaunchKernelGGL(distinct_fold_sum_tile_kernel, dim3(grid_cap(nrows, kBlock, 8192)), dim3(kBlock), 0, st, sorted, cbits,
+                     off, nbase, dictd, dicti, sumd, sumi, partd, parti);
+  hipLaunchKernelGGL(distinct_fold_sum_span_kernel, dim3(grid_cap(nbase * kBlock, kBlock, 8192)), dim3(kBlock), 0, st, off,
+                     nbase, (const double*)partd, (const uint64_t*)parti, sumd, sumi);
   return hipGetLastError();
 }
 

@@ -399,10 +399,11 @@ def local_key_values(segments, column: str, executor=None) -> list:
 
 def key_columns(qc) -> list:
     """Columns whose key space must be global for a cross-rank merge: the GROUP BY columns, and the
-    DISTINCTCOUNT columns (their device queries group by them too)."""
+    DISTINCTCOUNT / PERCENTILE / DISTINCTSUM / DISTINCTAVG columns (their device queries group by them too)."""
+    from .query import VALUE_SET_FUNCS
     cols = list(qc.group_by)
     for a in qc.aggregations:
-        if a.func == "DISTINCTCOUNT" and a.column not in cols:
+        if a.func in VALUE_SET_FUNCS and a.column not in cols:
             cols.append(a.column)
     return cols
 

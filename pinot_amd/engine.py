@@ -25,15 +25,15 @@ import numpy as np
 
 from . import _lib
 from ._lib import ColumnSpec, PredicateSpec, check, lib
-from .query import (DistinctSize, JavaDouble, QueryContext, fold_distinct_count, parse_sql, reduce_rows,
-                    server_table, sets_from_csr, split_distinct_count)
+from .query import (VALUE_SET_FUNCS, DistinctSize, FinalValue, JavaDouble, QueryContext, fold_distinct_count,
+                    hists_from_csr, parse_sql, reduce_rows, server_table, sets_from_csr, split_distinct_count)
 from .segment import ColumnBuffers, SegmentBuffers, DOUBLE, FLOAT, INT, LONG, STRING
 
 TYPE_CODE = {INT: 0, LONG: 1, FLOAT: 2, DOUBLE: 3, STRING: 4}
 ENC_CODE = {"FIXED_BIT": 0, "RAW": 1, "SORTED": 2}
 PRED_CODE = {"EQ": 0, "NOT_EQ": 1, "IN": 2, "NOT_IN": 3, "RANGE": 4}
 AGG_CODE = {"COUNT": 0, "SUM": 1, "MIN": 2, "MAX": 3, "SUMLONG": 4, "AVG": 5, "MINMAXRANGE": 6,
-            "DISTINCTCOUNT": 7}
+            "DISTINCTCOUNT": 7, "PERCENTILE": 8, "DISTINCTSUM": 9, "DISTINCTAVG": 10}
 EXPR_CODE = {"MUL": 1, "SUB": 2, "ADD": 3}
 
 
@@ -174,8 +174,9 @@ def _predicate_spec(pred, column: ColumnBuffers, use_inverted: bool, keep: list)
 
 
 class DistinctCountResult:
-    """Result of a query with DISTINCTCOUNT aggregations (query.split_distinct_count): the base
-    result plus one grouped result per DISTINCTCOUNT, folded into per-group value sets."""
+    """Result of a query with DISTINCTCOUNT / PERCENTILE / DISTINCTSUM / DISTINCTAVG aggregations
+    (query.split_distinct_count): the base result plus one grouped result per such column, folded into per-group
+    value sets and histograms."""
 
     def __init__(self, qc, base, subs, server_trim: bool = False):
         self.qc, self._base, self._subs = qc, base, subs
@@ -245,7 +246,8 @@ class QueryResult:
         self._h = handle
         self.qc = qc
         # per qc aggregation: ('direct', native_idx) | ('avg', sum_idx, count_idx) | ('range', native_idx) |
-        # ('distinct', native_idx, stored type of the column): DISTINCTCOUNT executed by the library
+        # ('distinct', native_idx, stored type of the column): DISTINCTCOUNT executed by the library |
+        # ('hist', ...) PERCENTILE | ('dset', ...) DISTINCTSUM / DISTINCTAVG, likewise
         self._agg_slots = agg_slots
         self._key_types = key_types
         self._merged_reached = None      # numGroupsLimitReached OR-ed over ranks by dist.merge_result
@@ -401,11 +403,28 @@ class QueryResult:
                        for i in np.unique(vals)}
         return sets_from_csr(off, vals, stored_type, strings)
 
+    def value_hists(self, native_idx: int, stored_type: str, num_groups: int) -> List[dict]:
+        """The histograms of library aggregation `native_idx` (a PERCENTILE), one dict distinct_value -> matching
+        docs per group in fetch order (pinot_amd_result_fetch_value_counts -> query.hists_from_csr)."""
+        L = lib()
+        total = C.c_int64()
+        check(L.pinot_amd_result_fetch_value_counts(self._h, native_idx, 0, None, None, None, C.byref(total)),
+              "fetch_value_counts")
+        off = np.zeros(num_groups + 1, dtype=np.int64)
+        vals = np.zeros(max(total.value, 1), dtype=np.int64)
+        cnts = np.zeros(max(total.value, 1), dtype=np.int64)
+        p64 = C.POINTER(C.c_int64)
+        check(L.pinot_amd_result_fetch_value_counts(self._h, native_idx, total.value, off.ctypes.data_as(p64),
+                                                    vals.ctypes.data_as(p64), cnts.ctypes.data_as(p64),
+                                                    C.byref(total)), "fetch_value_counts")
+        return hists_from_csr(off, vals[:total.value], cnts[:total.value], stored_type)
+
     def groups(self, arrays=None, distinct_sizes: bool = False) -> Dict[tuple, list]:
         """key tuple (group-by values; () for aggregation-only) -> intermediate result per aggregation.
         Converted column-wise (numpy -> Python lists, zipped), not group by group. `arrays`: the output of
         an earlier fetch_arrays() of this execution (not fetched again). distinct_sizes: a library-executed
-        DISTINCTCOUNT's partial is only its size (query.DistinctSize, from the fetch) instead of the value set."""
+        DISTINCTCOUNT's partial is only its size (query.DistinctSize, from the fetch) instead of the value set, a
+        PERCENTILE's / DISTINCTSUM's / DISTINCTAVG's only its final value (query.FinalValue)."""
         L = lib()
         got, keys, vals, vals_i, pairs = self.fetch_arrays() if arrays is None else arrays
         n = got.value
@@ -436,6 +455,13 @@ class QueryResult:
             elif slot[0] == "distinct":
                 if distinct_sizes:
                     acols.append([DistinctSize(c) for c in vi[:, slot[1]].tolist()])
+                else:
+                    acols.append(self.distinct_sets(slot[1], slot[2], n))
+            elif slot[0] in ("hist", "dset"):  # PERCENTILE / DISTINCTSUM / DISTINCTAVG executed by the library
+                if distinct_sizes:
+                    acols.append([FinalValue(x) for x in v[:, slot[1]].tolist()])
+                elif slot[0] == "hist":
+                    acols.append(self.value_hists(slot[1], slot[2], n))
                 else:
                     acols.append(self.distinct_sets(slot[1], slot[2], n))
             elif slot[0] == "range":
@@ -479,7 +505,8 @@ class ServerQueryExecutor:
     ORDER BY otherwise; pinot_amd_query_set_result_limit). Off by default: every group is returned,
     which is what a multi-server broker reduce over exact partials wants.
 
-    distinct_count: how a query with DISTINCTCOUNT aggregations runs. "mirror" (default): split here into the
+    distinct_count: how a query with DISTINCTCOUNT, PERCENTILE, DISTINCTSUM or DISTINCTAVG aggregations (each
+    where DISTINCTCOUNT is named below) runs. "mirror" (default): split here into the
     base query and one (group, value) query per DISTINCTCOUNT, every pair fetched and folded into Python sets
     (DistinctCountResult; the path multi-GPU merges use). "native": the whole query goes to the library, which
     runs the same queries and folds them on the device (PINOT_AMD_AGG_DISTINCTCOUNT); rows() then fetches only
@@ -545,16 +572,16 @@ class ServerQueryExecutor:
         its global key space (dist.global_key_space: the union of every rank's dictionaries), so that
         every rank's dense group table indexes the same groups."""
         qc = parse_sql(query) if isinstance(query, str) else query
-        if any(a.func == "DISTINCTCOUNT" for a in qc.aggregations) and self.distinct_count == "native":
+        if any(a.func in VALUE_SET_FUNCS for a in qc.aggregations) and self.distinct_count == "native":
             if key_space is not None:
                 raise _lib.PinotAmdError("distinct_count='native' takes no key_space: results of several ranks merge "
                                          "their value sets by union on the mirror path (distinct_count='mirror', "
                                          "DistinctCountResult.results())")
             for a in qc.aggregations:
-                if a.func == "DISTINCTCOUNT" and (a.expr is not None or a.column == "*"):
-                    raise ValueError("DISTINCTCOUNT takes one column")
+                if a.func in VALUE_SET_FUNCS and (a.expr is not None or a.column == "*"):
+                    raise ValueError(f"{a.func} takes one column")
             return self._execute(qc, segments, stream, None)
-        if any(a.func == "DISTINCTCOUNT" for a in qc.aggregations):
+        if any(a.func in VALUE_SET_FUNCS for a in qc.aggregations):
             # the device queries run untrimmed (a result limit on a (group, value) sub-query would cut value
             # sets); the server's combine table applies to the folded groups (DistinctCountResult.groups)
             trim = self.server_trim and bool(qc.group_by)
@@ -613,12 +640,16 @@ class ServerQueryExecutor:
             native = []
             agg_slots = []
 
-            def add(func, column, expr=None):
-                key = (func, column)
+            def add(func, column, expr=None, param=None):
+                key = (func, column) if param is None else (func, column, param)
                 if key in native:
                     return native.index(key)
                 idx = C.c_int32()
-                if expr is None:
+                if AGG_CODE[func] > AGG_CODE["DISTINCTCOUNT"]:  # the functions with a literal argument's entry point
+                    check(L.pinot_amd_query_add_aggregation_param(qh, AGG_CODE[func], column.encode(),
+                                                                  0.0 if param is None else param, C.byref(idx)),
+                          f"add_aggregation_param({func})")
+                elif expr is None:
                     check(L.pinot_amd_query_add_aggregation(qh, AGG_CODE[func], column.encode(), C.byref(idx)),
                           f"add_aggregation({func})")
                 else:
@@ -636,6 +667,12 @@ class ServerQueryExecutor:
                     if col is None:
                         raise _lib.PinotAmdError(f"unknown column {a.column!r} in segment {first.name}")
                     agg_slots.append(("distinct", add("DISTINCTCOUNT", a.column), col.stored_type))
+                elif a.func in VALUE_SET_FUNCS:    # PERCENTILE / DISTINCTSUM / DISTINCTAVG, likewise
+                    col = first.columns.get(a.column)
+                    if col is None:
+                        raise _lib.PinotAmdError(f"unknown column {a.column!r} in segment {first.name}")
+                    agg_slots.append(("hist" if a.func == "PERCENTILE" else "dset",
+                                      add(a.func, a.column, None, a.param), col.stored_type))
                 elif a.func == "MINMAXRANGE":  # MinMaxRangePair (min, max), NaN-skipping, in the library
                     agg_slots.append(("range", add("MINMAXRANGE", a.column, a.expr)))
                 else:
@@ -646,7 +683,7 @@ class ServerQueryExecutor:
                 for kind, idx, asc in qc.order_by_targets():
                     if kind == 1:  # the library aggregation whose final value orders (AVG: sum / count)
                         a = qc.aggregations[idx]
-                        idx = add(a.func, a.column, a.expr)
+                        idx = add(a.func, a.column, a.expr, a.param)
                     check(L.pinot_amd_query_add_order_by(qh, kind, idx, 1 if asc else 0), "add_order_by")
             arr = (C.c_void_p * len(segments))(*[s.handle.value for s in segments])
             rh = C.c_void_p()

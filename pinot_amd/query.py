@@ -18,7 +18,11 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-AGG_FUNCS = ("COUNT", "SUM", "MIN", "MAX", "AVG", "SUMLONG", "MINMAXRANGE", "DISTINCTCOUNT")
+AGG_FUNCS = ("COUNT", "SUM", "MIN", "MAX", "AVG", "SUMLONG", "MINMAXRANGE", "DISTINCTCOUNT", "PERCENTILE",
+             "DISTINCTSUM", "DISTINCTAVG")
+# the aggregations answered from a (group-by columns..., column) COUNT(*) query: each group's histogram over the
+# column's distinct values (split_distinct_count)
+VALUE_SET_FUNCS = ("DISTINCTCOUNT", "PERCENTILE", "DISTINCTSUM", "DISTINCTAVG")
 DEFAULT_GROUP_BY_LIMIT = 10          # Pinot's default LIMIT for group-by results
 DEFAULT_NUM_GROUPS_LIMIT = 100_000   # InstancePlanMakerImplV2.DEFAULT_NUM_GROUPS_LIMIT
 
@@ -104,6 +108,37 @@ EXPR_OPS = {"*": "MUL", "-": "SUB", "+": "ADD"}
 EXPR_FUNC = {"MUL": "times", "SUB": "minus", "ADD": "plus"}
 
 
+def agg_text(func: str, column: str, param=None) -> str:
+    """percentile50(c) for PERCENTILE50(c), PERCENTILE(c, 50) and PERCENTILE(c, '50') alike; percentile(c,99.9)."""
+    if func == "PERCENTILE":
+        p = float(param)
+        return f"percentile{int(p)}({column})" if p.is_integer() else f"percentile({column},{p!r})"
+    return f"{func.lower()}({column})"
+
+
+_PERCENTILE_N = re.compile(r"^PERCENTILE(\d{1,3})$")
+
+
+def check_percentile(p) -> float:
+    """AggregationFunctionFactory.java:534-536: 0 <= percentile <= 100."""
+    p = float(p)
+    if not 0.0 <= p <= 100.0:  # NaN fails both comparisons
+        raise ValueError(f"percentile {p!r} not in [0, 100]")
+    return p
+
+
+def agg_head(word: str):
+    """(function, percentile or None) when `word` names an aggregation function -- PERCENTILE with up to three
+    digits after the name carries its percentile (AggregationFunctionFactory.java:143,191) -- else None."""
+    w = word.upper()
+    if w in AGG_FUNCS:
+        return w, None
+    m = _PERCENTILE_N.match(w)
+    if m:
+        return "PERCENTILE", check_percentile(m.group(1))
+    return None
+
+
 @dataclasses.dataclass
 class Aggregation:
     """AggregationFunction over a column or a binary arithmetic transform of two columns.
@@ -113,14 +148,20 @@ class Aggregation:
     expr: None for a plain column, else (op, column_a, column_b) with op MUL / SUB / ADD
     (MultiplicationTransformFunction / SubtractionTransformFunction / AdditionTransformFunction;
     CAST(x AS DOUBLE) operands are accepted: every transform already computes in double)."""
-    func: str          # COUNT SUM MIN MAX AVG SUMLONG MINMAXRANGE DISTINCTCOUNT
+    func: str          # COUNT SUM MIN MAX AVG SUMLONG MINMAXRANGE DISTINCTCOUNT PERCENTILE DISTINCTSUM DISTINCTAVG
     column: str
     alias: Optional[str] = None
     expr: Optional[Tuple[str, str, str]] = None
+    param: Optional[float] = None   # PERCENTILE: the percentile, 0 <= param <= 100
+
+    @property
+    def text(self) -> str:
+        """The function's canonical text (what ORDER BY names when there is no alias)."""
+        return agg_text(self.func, self.column, self.param)
 
     @property
     def name(self) -> str:
-        return self.alias or f"{self.func.lower()}({self.column})"
+        return self.alias or self.text
 
     @property
     def columns(self) -> Tuple[str, ...]:
@@ -166,7 +207,7 @@ class QueryContext:
                 if e == g.lower():
                     hit = (0, j)
             for i, a in enumerate(self.aggregations):
-                if e in (a.name.lower().replace(" ", ""), f"{a.func.lower()}({a.column})".lower().replace(" ", "")):
+                if e in (a.name.lower().replace(" ", ""), a.text.lower().replace(" ", "")):
                     hit = (1, i)
             if hit is None:
                 raise ValueError(f"ORDER BY {expr} not in select list")
@@ -251,8 +292,8 @@ class _Parser:
         aggs, cols = [], []
         while True:
             tok = self.peek()
-            if tok[0] == "id" and tok[1].upper() in AGG_FUNCS and self.peek(1) == ("op", "("):
-                func = tok[1].upper()
+            if tok[0] == "id" and agg_head(tok[1]) and self.peek(1) == ("op", "("):
+                func, param = agg_head(tok[1])
                 self.i += 2
                 expr = None
                 if self.peek() == ("op", "*"):
@@ -266,6 +307,7 @@ class _Parser:
                         col2 = self.operand()
                         expr = (op, col, col2)
                         col = f"{EXPR_FUNC[op]}({col},{col2})"
+                param = self.percentile_arg(func, param)
                 self.eat_op(")")
                 alias = None
                 if self.kw("AS"):
@@ -273,7 +315,7 @@ class _Parser:
                     alias = self.ident()
                 elif self.peek()[0] == "id" and self.peek()[1].upper() not in ("FROM",):
                     alias = self.ident()   # implicit alias: sum(x) revenue
-                aggs.append(Aggregation(func, col, alias, expr))
+                aggs.append(Aggregation(func, col, alias, expr, param))
             else:
                 cols.append(self.ident())
             if self.peek() == ("op", ","):
@@ -309,6 +351,24 @@ class _Parser:
             raise ValueError(f"unexpected trailing token {self.peek()}")
         return QueryContext(table, aggs, group_by, flt, order, limit, cols)
 
+    def percentile_arg(self, func, param):
+        """PERCENTILE(c, 50) / PERCENTILE(c, 99.9) / PERCENTILE(c, '50'): the second argument, unless the
+        function's name carried the percentile."""
+        if func != "PERCENTILE":
+            return None
+        if self.peek() == ("op", ","):
+            if param is not None:
+                raise ValueError("PERCENTILE<n>(column) takes one argument")
+            self.i += 1
+            lit = self.literal()
+            try:
+                param = check_percentile(lit)
+            except (TypeError, ValueError):
+                raise ValueError(f"bad percentile {lit!r}") from None
+        if param is None:
+            raise ValueError("PERCENTILE needs its percentile: PERCENTILE50(c) or PERCENTILE(c, 50)")
+        return param
+
     def operand(self) -> str:
         """A column, optionally as CAST(column AS type) (the cast does not change the value the
         arithmetic transforms compute: they read every argument as double)."""
@@ -325,13 +385,14 @@ class _Parser:
 
     def order_item(self):
         tok = self.peek()
-        if tok[0] == "id" and tok[1].upper() in AGG_FUNCS and self.peek(1) == ("op", "("):
-            func = tok[1].upper()
+        if tok[0] == "id" and agg_head(tok[1]) and self.peek(1) == ("op", "("):
+            func, param = agg_head(tok[1])
             self.i += 2
             col = "*" if self.peek() == ("op", "*") else self.peek()[1]
             self.i += 1
+            param = self.percentile_arg(func, param)
             self.eat_op(")")
-            expr = f"{func.lower()}({col})"
+            expr = agg_text(func, col, param)
         else:
             expr = self.ident()
         asc = True
@@ -474,9 +535,11 @@ def _parse_sql(sql: str) -> QueryContext:
 
 
 # ---------------------------------------------------------------------------------------- reduce
-def final_value(func: str, partial):
+def final_value(func: str, partial, param=None):
     """AggregationFunction.extractFinalResult: AVG -> sum / count, MINMAXRANGE -> max - min
-    (MinMaxRangeAggregationFunction: MinMaxRangePair(+inf, -inf) when no doc matched), others unchanged."""
+    (MinMaxRangeAggregationFunction: MinMaxRangePair(+inf, -inf) when no doc matched), DISTINCTCOUNT -> the set's
+    size, PERCENTILE (param: the percentile) -> percentile_select over the histogram, DISTINCTSUM / DISTINCTAVG ->
+    the set's sum (/ its size), others unchanged."""
     if func == "AVG":
         s, c = partial
         return s / c if c else float("-inf")
@@ -485,7 +548,19 @@ def final_value(func: str, partial):
         return mx - mn
     if func == "DISTINCTCOUNT":
         return len(partial)
-    return partial
+    if func not in _HISTOGRAM_FINALS:  # (one look-up on the path of the plain aggregations)
+        return partial
+    if isinstance(partial, FinalValue):
+        return partial.v
+    if func == "PERCENTILE":
+        return percentile_select(partial, param)
+    if func == "DISTINCTSUM":
+        return distinct_sum(partial)
+    # DistinctAvgAggregationFunction.java:83-95: 0.0 / 0 = NaN for the empty set
+    return distinct_sum(partial) / len(partial) if len(partial) else float("nan")
+
+
+_HISTOGRAM_FINALS = frozenset(("PERCENTILE", "DISTINCTSUM", "DISTINCTAVG"))
 
 
 def merge_partial(func: str, a, b):
@@ -500,8 +575,13 @@ def merge_partial(func: str, a, b):
         return (a[0] + b[0], a[1] + b[1])
     if func == "MINMAXRANGE":
         return (min(a[0], b[0]), max(a[1], b[1]))
-    if func == "DISTINCTCOUNT":
+    if func in ("DISTINCTCOUNT", "DISTINCTSUM", "DISTINCTAVG"):
         return a | b
+    if func == "PERCENTILE":  # histograms (distinct_value -> matching docs) add
+        out = dict(a)
+        for v, c in b.items():
+            out[v] = out.get(v, 0) + c
+        return out
     raise ValueError(func)
 
 
@@ -511,14 +591,20 @@ def split_distinct_count(qc: QueryContext):
     among the matching docs (intermediate = the set, merge = union, final = its size). Planned as
     device queries: the query without its DISTINCTCOUNTs (or COUNT(*) if nothing else is left), and
     per DISTINCTCOUNT(c) the same filter grouped by (group-by columns..., c) — each distinct c of a
-    group is one group of that query. Returns (base query, [(aggregation index, sub query)])."""
-    rest = [a for a in qc.aggregations if a.func != "DISTINCTCOUNT"]
+    group is one group of that query. PERCENTILE, DISTINCTSUM and DISTINCTAVG read the same query (its COUNT is
+    the number of docs holding the value: the group's histogram), so every such aggregation on one column shares
+    one sub query, listed under the first of them. Returns (base query, [(aggregation index, sub query)])."""
+    rest = [a for a in qc.aggregations if a.func not in VALUE_SET_FUNCS]
     base = dataclasses.replace(qc, aggregations=rest or [Aggregation("COUNT", "*")], order_by=[])
     subs = []
+    seen = set()
     for i, a in enumerate(qc.aggregations):
-        if a.func == "DISTINCTCOUNT":
+        if a.func in VALUE_SET_FUNCS:
             if a.expr is not None or a.column == "*":
-                raise ValueError("DISTINCTCOUNT takes one column")
+                raise ValueError(f"{a.func} takes one column")
+            if a.column in seen:   # PERCENTILE / DISTINCTSUM / DISTINCTAVG / DISTINCTCOUNT of one column share
+                continue           # its query: the sub query of the first of them (fold_distinct_count)
+            seen.add(a.column)
             subs.append((i, dataclasses.replace(qc, aggregations=[Aggregation("COUNT", "*")], order_by=[],
                                                 group_by=list(qc.group_by) + [a.column],
                                                 num_groups_limit=max(qc.num_groups_limit, 1 << 30))))
@@ -569,21 +655,98 @@ def fold_distinct_count(qc: QueryContext, base_groups: dict, sub_groups: Sequenc
     """Groups of the original query from split_distinct_count's results (same group keys as the
     base query: a group exists iff a doc matched, in every one of the queries alike). Keys and set
     elements are matched by distinct_value (bit patterns for floats), never by Python float equality."""
-    sets = {i: {} for i, _ in sub_groups}
+    # per sub query: group -> value set, or -- when a PERCENTILE reads the column -- group -> histogram
+    # (distinct_value -> matching docs: the sub query's COUNT(*))
+    by_column = {qc.aggregations[i].column: i for i, _ in sub_groups}
+    counted = {by_column[a.column] for a in qc.aggregations if a.func == "PERCENTILE"}
+    hists = {i: {} for i, _ in sub_groups}
     for i, g in sub_groups:
-        for key in g:
-            sets[i].setdefault(canonical_key(key[:-1]), set()).add(distinct_value(key[-1]))
-    rest_idx = [j for j, a in enumerate(qc.aggregations) if a.func != "DISTINCTCOUNT"]
+        if i in counted:
+            for key, parts in g.items():
+                h = hists[i].setdefault(canonical_key(key[:-1]), {})
+                v = distinct_value(key[-1])
+                h[v] = h.get(v, 0) + int(parts[0])
+        else:
+            for key in g:
+                hists[i].setdefault(canonical_key(key[:-1]), set()).add(distinct_value(key[-1]))
+    rest_idx = [j for j, a in enumerate(qc.aggregations) if a.func not in VALUE_SET_FUNCS]
     out = {}
     for key, parts in base_groups.items():
         full = [None] * len(qc.aggregations)
         for j, p in zip(rest_idx, parts):
             full[j] = p
         ck = canonical_key(key)
-        for i in sets:
-            full[i] = frozenset(sets[i].get(ck, ()))
+        for j, a in enumerate(qc.aggregations):
+            if a.func in VALUE_SET_FUNCS:
+                h = hists[by_column[a.column]].get(ck, {})
+                full[j] = dict(h) if a.func == "PERCENTILE" else frozenset(h)
         out[key] = full
     return out
+
+
+def _value_as_double(v) -> float:
+    """The double a set element / histogram key (distinct_value) stands for."""
+    if isinstance(v, tuple):
+        return struct.unpack("<d", struct.pack("<q", v[1]))[0]
+    return float(v)
+
+
+def percentile_select(hist, p) -> float:
+    """PercentileAggregationFunction.java:207-252 over a histogram (distinct_value -> matching docs) instead of
+    the DoubleArrayList it stands for: the values sorted as Arrays.sort(double[]) sorts them (-0.0 < 0.0, NaN
+    greatest and one value); n docs: the last value for p = 100, else the one at index
+    (int) ((double) n * p / 100.0) -- one double multiply, one double divide, truncated; no doc: -inf
+    (DEFAULT_FINAL_RESULT). The native path and the mirror path both end here or in the kernel that restates it."""
+    n = sum(hist.values())
+    if n == 0:
+        return float("-inf")
+    idx = n - 1 if p == 100 else min(int(float(n) * float(p) / 100.0), n - 1)
+    cum = 0
+    last = None
+    for v, c in sorted(((_value_as_double(k), c) for k, c in hist.items()), key=lambda t: _double_order(t[0])):
+        cum += c
+        last = v
+        if cum > idx:
+            break
+    return last
+
+
+def distinct_sum(values) -> float:
+    """DistinctSumAggregationFunction.java:83-95 over DISTINCTCOUNT's set: the sum of the represented values as a
+    double (0.0 for the empty set). Integers sum exactly and round once; floats go through math.fsum (Pinot sums in
+    hash-set order: its result is only defined up to that order)."""
+    if all(not isinstance(v, tuple) for v in values):
+        return float(sum(int(v) for v in values))
+    return 0.0 + math.fsum(_value_as_double(v) for v in values)
+
+
+class FinalValue:
+    """A partial known only by its final value (QueryResult.rows() of a natively executed PERCENTILE / DISTINCTSUM /
+    DISTINCTAVG reads the value the library computed, not the histogram): final_value returns it."""
+    __slots__ = ("v",)
+
+    def __init__(self, v):
+        self.v = v
+
+
+def hists_from_csr(offsets, values, counts, stored_type: str) -> List[dict]:
+    """The per-group PERCENTILE partials from the library's CSR (pinot_amd_result_fetch_value_counts): group g's
+    entries of `values` (fetch's key encoding) and `counts`. One dict distinct_value -> matching docs per group."""
+    off = np.asarray(offsets, dtype=np.int64)
+    vals = np.ascontiguousarray(np.asarray(values, dtype=np.int64))
+    cnts = np.asarray(counts, dtype=np.int64).tolist()
+    if off.size == 0:
+        return []
+    if off[0] != 0 or np.any(np.diff(off) < 0) or off[-1] > vals.size or off[-1] > len(cnts):
+        raise ValueError("malformed CSR offsets")
+    if stored_type == "STRING":
+        raise ValueError("a histogram of STRING values has no percentile")
+    if stored_type in ("FLOAT", "DOUBLE"):
+        items = [distinct_value(f) for f in vals.view(np.float64).tolist()]
+    else:
+        items = vals.tolist()
+    o = off.tolist()
+    return [dict(zip(items[o[g]:o[g + 1]], cnts[o[g]:o[g + 1]])) for g in range(len(o) - 1)]
 
 
 def sets_from_csr(offsets, values, stored_type: str, strings=None) -> List[frozenset]:
@@ -666,7 +829,7 @@ def server_table(qc: QueryContext, groups: dict) -> dict:
     def sort_key(k):
         out = []
         for kind, idx, asc in targets:
-            o = _dict_order(k[idx]) if kind == 0 else _double_order(final_value(qc.aggregations[idx].func, groups[k][idx]))
+            o = _dict_order(k[idx]) if kind == 0 else _double_order(final_value(qc.aggregations[idx].func, groups[k][idx], qc.aggregations[idx].param))
             out.append(o if asc else _Reverse(o))
         return tuple(out) + (rank[k],)
     ordered = sorted(keys, key=sort_key)
@@ -687,9 +850,9 @@ def reduce_rows(qc: QueryContext, groups: dict) -> List[tuple]:
     """
     rows = []
     for key, parts in groups.items():
-        rows.append(tuple(key) + tuple(final_value(a.func, p) for a, p in zip(qc.aggregations, parts)))
+        rows.append(tuple(key) + tuple(final_value(a.func, p, a.param) for a, p in zip(qc.aggregations, parts)))
     names = list(qc.group_by) + [a.name for a in qc.aggregations]
-    exprs = list(qc.group_by) + [f"{a.func.lower()}({a.column})" for a in qc.aggregations]
+    exprs = list(qc.group_by) + [a.text for a in qc.aggregations]
     for expr, asc in reversed(qc.order_by):
         e = expr.lower()
         idx = None
