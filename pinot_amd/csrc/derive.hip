@@ -18,6 +18,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "device_types.h"
+#include "kernels.h"
 
 namespace pamd {
 

@@ -30,95 +30,7 @@
 #include "../../include/pinot_amd.h"
 #include "device_types.h"
 #include "jit.h"
-
-namespace pamd {
-hipError_t launch_init_acc(uint64_t* d_acc, const DevQuery& q, int64_t num_keys, hipStream_t st);
-hipError_t launch_sext_hi(uint64_t* d_acc, int64_t n, const int32_t* arrs, int32_t narr, hipStream_t st);
-hipError_t launch_raw_int_minmax(const uint8_t* be, int type, int64_t n, long long* out, hipStream_t st);
-hipError_t launch_fingerprint(const void* p, size_t bytes, unsigned long long* out, hipStream_t st);
-hipError_t launch_for_pack(const uint8_t* be, int type, int64_t n, unsigned long long base, int lo_bits, int hi_bits,
-                           uint8_t* lo, uint8_t* hi, hipStream_t st);
-hipError_t launch_trim(const unsigned long long* keys, int64_t cap, int nw_seg, const uint64_t* acc, int fd_acc,
-                       int32_t nsegs, int64_t limit, const int64_t* bucket_base, uint32_t* hist,
-                       unsigned long long* seg_distinct, int64_t* bstar, int64_t* rank, unsigned long long* bitmap,
-                       int64_t* dstar, unsigned long long* limit_reached, hipStream_t st);
-hipError_t launch_hash_merge(const unsigned long long* skeys, int64_t scap, int nw, int has_seg, const uint64_t* sacc,
-                             unsigned long long* fkeys, int64_t fcap, uint64_t* facc, const DevQuery& q, int fd_acc,
-                             const int64_t* dstar, unsigned long long* overflow, hipStream_t st,
-                             const SegSelStage* sst = nullptr, int nst = 0, const int32_t* sdone = nullptr,
-                             const uint64_t* scut = nullptr);
-hipError_t launch_segsel(const unsigned long long* keys, int64_t cap, int nw, const uint64_t* acc, int fd_acc,
-                         const int64_t* dstar, const DevQuery& q, const SegSelStage* sst, int nst, int32_t nsegs,
-                         int64_t keep, unsigned long long* cnt, int64_t* want, int32_t* done, uint64_t* prefix,
-                         uint64_t* cut, uint32_t* hist, hipStream_t st);
-hipError_t launch_admit(uint32_t* first, int64_t nk, const uint32_t* seen, const unsigned long long* seen_n, int64_t cap,
-                        int32_t nsegs, int64_t limit, const int64_t* bucket_base, int64_t max_buckets, uint32_t* hist,
-                        int64_t* bstar, int64_t* rank, unsigned long long* bitmap, int64_t* dstar,
-                        unsigned long long* limit_reached, int phase, uint32_t* admit, int64_t words, hipStream_t st);
-hipError_t launch_presence_bitset(const uint64_t* count, int64_t n, unsigned long long* bits, hipStream_t st);
-hipError_t launch_seg_cut(const unsigned long long* bits, int64_t words, int32_t nsegs, int64_t limit,
-                          unsigned long long* cut, hipStream_t st);
-hipError_t launch_spill_direct_prep(const int64_t* offs, const int64_t* part_begin, const uint32_t* hist, int P,
-                                    int64_t grid, int64_t* dbase, uint32_t* dcnt, int64_t* pbeg, hipStream_t st);
-hipError_t launch_spill_agg(const DevHash& H, int nw, const unsigned long long* sorted, const int64_t* part_begin,
-                            const DevQuery& q, uint64_t* acc, int agg_grid, int S, uint32_t narrow, hipStream_t st);
-hipError_t launch_spill_passes(const DevHash& H, int nw, int64_t grid, const uint32_t* hist_unused, int64_t* offs,
-                               int64_t* part_begin, unsigned long long* sorted, const DevQuery& q, uint64_t* acc,
-                               int agg_grid, int S, int sorted_scatter, uint32_t narrow, hipStream_t st);
-hipError_t launch_gather_groups(const int32_t* slots, int64_t ngroups, const unsigned long long* keys, int nw,
-                                int64_t cap, const uint64_t* acc, int32_t nacc, uint64_t* out_keys, uint64_t* out_acc,
-                                hipStream_t st);
-hipError_t launch_export_groups(const int32_t* slots, int64_t ngroups, const unsigned long long* hkeys, int64_t cap,
-                                const uint64_t* acc, int32_t nacc_out, const DevKeyPack& kp, uint64_t* out_keys,
-                                uint64_t* out_acc, hipStream_t st);
-hipError_t launch_merge_rows(const uint64_t* keys, const uint64_t* acc, int64_t n, int nw, int nacc_in,
-                             unsigned long long* fkeys, int64_t fcap, uint64_t* facc, const DevQuery& q,
-                             unsigned long long* overflow, hipStream_t st);
-hipError_t launch_distinct_fold_count(const uint64_t* ckeys, int64_t nrows, const DevKeyPack& kc, const DevKeyPack& kb,
-                                      const uint64_t* bkeys, int64_t nbase, int cbits, uint32_t* cnt, uint64_t* pair,
-                                      unsigned long long* miss, hipStream_t st);
-hipError_t launch_distinct_fold_fill(const uint64_t* sorted, int64_t nrows, int cbits, const uint32_t* cnt, int64_t nbase,
-                                     int64_t* off, int32_t* values, hipStream_t st);
-hipError_t launch_value_count_scan(const uint64_t* counts, int64_t n, int64_t* bsum, int64_t* cum, hipStream_t st);
-hipError_t launch_percentile_select(const int64_t* off, const int64_t* cum, const int32_t* values, int64_t ngroups,
-                                    const double* pct, int np, int32_t* out, hipStream_t st);
-int64_t distinct_fold_sum_tiles(int64_t nrows);
-hipError_t launch_distinct_fold_sum(const uint64_t* sorted, int64_t nrows, int cbits, const int64_t* off, int64_t nbase,
-                                    const double* dictd, const int64_t* dicti, double* sumd, uint64_t* sumi,
-                                    double* partd, uint64_t* parti, hipStream_t st);
-hipError_t launch_read_dict_ids(const uint8_t* packed, int bits, int64_t start, int64_t len, int32_t* out,
-                                hipStream_t st);
-hipError_t launch_pack_dict_ids(const int32_t* values, int64_t n, int bits, uint8_t* packed, hipStream_t st);
-size_t derive_dictionary_scratch(int64_t n);
-size_t sort_rows_scratch(int64_t n);
-hipError_t sort_rows_by_key(const uint64_t* keys, int nwk, const int* word_bits, const uint64_t* acc, int nacc, int64_t n,
-                            void* scratch, uint64_t* keys_out, uint64_t* acc_out, hipStream_t st);
-hipError_t derive_dictionary(const uint8_t* d_be, int type, int64_t n, void* d_scratch, int32_t* d_ids,
-                             uint8_t* d_dict_be, int64_t* h_card, hipStream_t st);
-hipError_t launch_read_raw(const uint8_t* raw, int type, int64_t start, int64_t len, uint8_t* out, hipStream_t st);
-hipError_t launch_chunk_decompress(const uint8_t* src, uint8_t* dst, const void* jobs, int32_t njobs, int32_t* status,
-                                   hipStream_t st);
-hipError_t launch_bitset_binop(const uint64_t* a, const uint64_t* b, uint64_t* out, int64_t n, int op,
-                               hipStream_t st);
-hipError_t launch_bitset_not(const uint64_t* a, uint64_t* out, int64_t num_docs, hipStream_t st);
-int64_t compact_num_chunks(int64_t num_docs);
-hipError_t launch_bitset_count(const uint64_t* bits, int64_t num_docs, int64_t* d_chunk_counts, int64_t* d_total,
-                               hipStream_t st);
-hipError_t launch_bitset_compact(const uint64_t* bits, int64_t num_docs, const int64_t* d_chunk_offsets,
-                                 int32_t* out, hipStream_t st);
-hipError_t launch_expand_jobs(const void* d_jobs, int32_t njobs, int64_t total_items, hipStream_t st);
-hipError_t launch_roaring_select(const void* d_jobs, const void* d_fs, int32_t nfs, int64_t total_items, const void* d_segs,
-                                 int32_t nleaves, int32_t nclauses, unsigned long long* sel_entries,
-                                 unsigned long long* sel_count, int64_t sel_cap, unsigned long long* matched_out, int clause,
-                                 hipStream_t st);
-hipError_t launch_pack_sel(const void* conts, const int32_t* sel, int64_t n, int group, unsigned long long* out,
-                           hipStream_t st);
-int expand_group();
-hipError_t launch_partition_offsets(const uint32_t* d_hist, int32_t nparts, int64_t nblocks, int64_t* d_offs,
-                                    int64_t* d_part_begin, hipStream_t st);
-hipError_t launch_allot_prefix(const uint32_t* d_hist, int32_t P, int64_t G, int mode, int64_t stride, double scale,
-                               int64_t limit, int64_t* d_ptot, int64_t* d_out, hipStream_t st);
-}  // namespace pamd
+#include "kernels.h"
 
 using namespace pamd;
 
@@ -145,9 +57,9 @@ static int fail(int code, const char* fmt, ...) {
 
 namespace {
 
-// Runtime knobs. A default build reads only the planner overrides the test suite exercises and the server's resource
-// limits (the list below); the experiment knobs of earlier rounds' sweeps (DESIGN.md records their outcomes) are
-// honoured only in a diagnostics build (-DPINOT_AMD_DIAGNOSTICS), so a default build plans from the query alone.
+// Runtime knobs: only the planner overrides the test suite exercises and the server's resource limits (the list
+// below) are read. The experiment knobs of earlier rounds' sweeps are gone, each fixed at the value its sweep chose
+// (DESIGN.md records the outcomes); any other name reads as unset, so the library plans from the query alone.
 static const std::set<std::string>& kept_knobs() {
   static const std::set<std::string> kept = {
       "PINOT_AMD_ADMIT_PREFIX",
@@ -196,22 +108,16 @@ static const std::set<std::string>& kept_knobs() {
   return kept;
 }
 static const char* knob(const char* name) {
-#ifndef PINOT_AMD_DIAGNOSTICS
   if (!kept_knobs().count(name)) return nullptr;
-#endif
   return getenv(name);
 }
-// every knob a default build reads, with its value: part of a prepared plan's identity (a plan built under other
-// overrides is another plan); empty in a diagnostics build, whose knobs are open-ended (no plan cache there)
+// every knob the library reads, with its value: part of a prepared plan's identity (a plan built under other
+// overrides is another plan)
 static std::string knob_snapshot() {
-#ifdef PINOT_AMD_DIAGNOSTICS
-  return std::string();
-#else
   std::string out = "knobs";
   for (const std::string& k : kept_knobs())
     if (const char* v = getenv(k.c_str())) out += "|" + k + "=" + v;
   return out;
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1546,7 +1452,7 @@ struct Launch {
   size_t shmem_direct = 0;
   DevBuf d_dbase, d_dcnt, d_dpbeg;
   int direct_lg = -1;
-  int grid = 1, atomic_grid = 1, sample_grid = 1, agg_grid = 1, scan_nsub = 1, part_sub = kPartSub;
+  int grid = 1, atomic_grid = 1, sample_grid = 1, agg_grid = 1, scan_nsub = 1;
   size_t shmem = 0, shmem_scatter = 0, shmem_agg = 0;
   DevPartition part{};
   int64_t docs = 0, tiles = 0;
@@ -1837,7 +1743,7 @@ static size_t plan_cache_budget() {
 
 static std::string plan_identity(const pinot_amd_query& Q, const std::vector<pinot_amd_segment*>& segs, bool filter_only) {
   const std::string ks = knob_snapshot();
-  if (ks.empty() || !plan_cache_on()) return std::string();
+  if (!plan_cache_on()) return std::string();
   std::string k = filter_only ? "F|" : "Q|";
   auto num = [&](long long v) { k += std::to_string(v) + ","; };
   k += preds_signature(Q.preds) + "|G";
@@ -2244,7 +2150,6 @@ static int make_leaf_uncached(pinot_amd_result* r, int si, const pinot_amd_segme
   return 0;
 }
 
-static bool env_is(const char* name, const char* val);
 static std::mutex g_leaf_mu;  // guards every segment's leaf_cache
 constexpr size_t kLeafCacheMax = 256;  // entries per segment (cleared when full)
 
@@ -2256,39 +2161,32 @@ static std::string leaf_cache_key(const PredSpec& p, int slot, bool decoded_anyw
          std::to_string(expand_group()) + "|" + (pol ? pol : "");
 }
 
-// key: leaf_cache_key(p, slot, decoded_anyway) when the caller built it once for every segment
+// key: leaf_cache_key(p, slot, decoded_anyway), built by the caller once for every segment
 static int make_leaf_for_segment(pinot_amd_result* r, int si, pinot_amd_segment* seg, const PredSpec& p,
                                  const Column& c, int slot, DevLeaf* L, bool* needs_slot, hipStream_t st,
-                                 bool decoded_anyway, const std::string* key_in = nullptr) {
-  const bool use_cache = key_in != nullptr || !env_is("PINOT_AMD_LEAF_CACHE", "0");
-  std::string key_own;
-  const std::string& key = key_in ? *key_in : key_own;
-  if (use_cache) {
-    if (!key_in) key_own = leaf_cache_key(p, slot, decoded_anyway);
-    std::shared_ptr<const LeafCacheEntry> e;
-    {
-      std::lock_guard<std::mutex> g(g_leaf_mu);
-      auto it = seg->leaf_cache.find(key);
-      if (it != seg->leaf_cache.end()) e = it->second;
+                                 bool decoded_anyway, const std::string& key) {
+  std::shared_ptr<const LeafCacheEntry> hit;
+  {
+    std::lock_guard<std::mutex> g(g_leaf_mu);
+    auto it = seg->leaf_cache.find(key);
+    if (it != seg->leaf_cache.end()) hit = it->second;
+  }
+  if (hit) {
+    *L = hit->L;
+    *needs_slot = hit->needs_slot;
+    for (auto& b : hit->bufs) r->shared.push_back(b);
+    if (hit->inv) {
+      auto bs = std::make_unique<DevBuf>();
+      if (int rc = bs->alloc(hit->bitset_alloc)) return rc;
+      L->bits = (const uint32_t*)bs->p;
+      r->inv_leaves.push_back({si, &c, bs.get(), hit->sel, hit->grp, hit->nsel, hit->nchunks, seg->num_docs,
+                               hit->alg_bytes, hit->bitset_bytes, hit->psel});
+      r->owned.push_back(std::move(bs));
     }
-    if (e) {
-      *L = e->L;
-      *needs_slot = e->needs_slot;
-      for (auto& b : e->bufs) r->shared.push_back(b);
-      if (e->inv) {
-        auto bs = std::make_unique<DevBuf>();
-        if (int rc = bs->alloc(e->bitset_alloc)) return rc;
-        L->bits = (const uint32_t*)bs->p;
-        r->inv_leaves.push_back({si, &c, bs.get(), e->sel, e->grp, e->nsel, e->nchunks, seg->num_docs, e->alg_bytes,
-                                 e->bitset_bytes, e->psel});
-        r->owned.push_back(std::move(bs));
-      }
-      return 0;
-    }
+    return 0;
   }
   const size_t o0 = r->owned.size(), i0 = r->inv_leaves.size();
   if (int rc = make_leaf_uncached(r, si, seg, p, c, slot, L, needs_slot, st, decoded_anyway)) return rc;
-  if (!use_cache) return 0;
   auto e = std::make_shared<LeafCacheEntry>();
   e->L = *L;
   e->needs_slot = *needs_slot;
@@ -2553,22 +2451,6 @@ static int launch_one(pinot_amd_result* r, Launch& L, size_t li, uint64_t* table
     else
       // (select kernels hold their tables in static LDS)
       HIP_OK(hipModuleLaunchKernel(L.jit->fn, (unsigned)L.grid, 1, 1, kBlock, 1, 1, 0, st, args, nullptr));
-    if (knob("PINOT_AMD_CHECK_SELECT")) {  // diagnostics: validate the vector on the host
-      unsigned long long ctr[2];
-      HIP_OK(hipMemcpyAsync(ctr, L.q.sel_count, 16, hipMemcpyDeviceToHost, st));
-      HIP_OK(hipStreamSynchronize(st));
-      if (ctr[1] != 0 || ctr[0] > (unsigned long long)L.q.sel_cap || ctr[0] % 4 != 0)
-        return fail(PINOT_AMD_EINVAL, "select check: count %llu overflow %llu cap %lld", ctr[0], ctr[1], (long long)L.q.sel_cap);
-      std::vector<unsigned long long> ent(ctr[0]);
-      if (!ent.empty()) HIP_OK(hipMemcpy(ent.data(), L.q.sel_entries, ent.size() * 8, hipMemcpyDeviceToHost));
-      std::vector<DevSegment> ds(L.segs.size());
-      HIP_OK(hipMemcpy(ds.data(), L.d_segs.p, ds.size() * sizeof(DevSegment), hipMemcpyDeviceToHost));
-      for (size_t i = 0; i < ent.size(); ++i) {
-        const uint32_t sg = (uint32_t)(ent[i] >> 32), d = (uint32_t)ent[i];
-        if (sg >= ds.size() || (d != 0xFFFFFFFFu && (int64_t)d >= ds[sg].num_docs) || (uint32_t)(ent[i & ~(size_t)3] >> 32) != sg)
-          return fail(PINOT_AMD_EINVAL, "select check: entry %zu = seg %u doc %u (segments %zu)", i, sg, d, ds.size());
-      }
-    }
     HIP_OK(hipModuleLaunchKernel(L.jit->fn_gather, (unsigned)L.gather_grid, 1, 1, (unsigned)L.gather_threads, 1, 1,
                                  (unsigned)L.shmem, st, args, nullptr));
     return 0;
@@ -2579,7 +2461,7 @@ static int launch_one(pinot_amd_result* r, Launch& L, size_t li, uint64_t* table
                                  (unsigned)(direct ? L.shmem_direct : L.shmem), st, args, nullptr));
     return 0;
   }
-  const unsigned pt = (unsigned)(kBlock * L.part_sub);
+  const unsigned pt = (unsigned)(kBlock * kPartSub);
   const unsigned count_grid = (unsigned)(L.grid * kPartCountRatio);
   if (L.part_sampled) {
     // per scatter block: strided histogram -> allotments -> (direct-atomic scan | scatter) -> records
@@ -2998,25 +2880,47 @@ extern "C" {
 // wall-clock milliseconds of the planning phases of one execute (diagnostics: where a cold / cached
 // query's host time goes)
 // hipModuleOccupancyMaxActiveBlocksPerMultiprocessor per (kernel, block size, dynamic LDS), memoised: the planner
-// asks for every launch of every execution, and a kernel's occupancy never changes
-static hipError_t occupancy_blocks(int* out, hipFunction_t fn, int threads, size_t shmem) {
+// asks for every launch of every execution, and a kernel's occupancy never changes. Returns the resident blocks
+// per CU, 1 when the runtime cannot tell or reports none.
+static int occupancy_blocks(hipFunction_t fn, int threads, size_t shmem) {
   static std::mutex mu;
   static std::map<std::tuple<const void*, int, size_t>, int> memo;
   const auto key = std::make_tuple((const void*)fn, threads, shmem);
   {
     std::lock_guard<std::mutex> g(mu);
     auto it = memo.find(key);
-    if (it != memo.end()) {
-      *out = it->second;
-      return hipSuccess;
-    }
+    if (it != memo.end()) return std::max(it->second, 1);
   }
-  const hipError_t e = hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(out, fn, threads, shmem);
-  if (e == hipSuccess) {
+  int blocks = 0;
+  if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, threads, shmem) != hipSuccess) return 1;
+  {
     std::lock_guard<std::mutex> g(mu);
-    memo[key] = *out;
+    memo[key] = blocks;
   }
-  return e;
+  return std::max(blocks, 1);
+}
+
+// largest |value| of a column over the segments (-1: some segment records no range)
+static __int128 column_maxabs(const std::vector<pinot_amd_segment*>& segs, const std::string& name) {
+  __int128 m = 0;
+  for (auto* s : segs) {
+    const Column& c = *s->cols.at(name);
+    if (!c.has_range) return -1;
+    const __int128 a = c.vmax < 0 ? -(__int128)c.vmax : (__int128)c.vmax;
+    const __int128 b = c.vmin < 0 ? -(__int128)c.vmin : (__int128)c.vmin;
+    m = std::max(m, std::max(a, b));
+  }
+  return m;
+}
+// largest |value| one doc adds to an integer SUM accumulator (-1: unknown)
+static __int128 acc_maxabs(const std::vector<pinot_amd_segment*>& segs, const std::vector<std::string>& slot_cols,
+                           const JitAcc& a) {
+  __int128 m = column_maxabs(segs, slot_cols[a.slot]);
+  if (m >= 0 && a.expr != EXPR_COL) {
+    const __int128 m2 = column_maxabs(segs, slot_cols[a.slot2]);
+    m = m2 < 0 ? -1 : a.expr == EXPR_MUL ? m * m2 : m + m2;
+  }
+  return m;
 }
 
 struct PlanClock {
@@ -3037,33 +2941,116 @@ struct PlanClock {
 };
 
 static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, int32_t n, void* stream,
-                        bool filter_only, pinot_amd_result** out) {
-  if (!qq || !segs_in || n < 1 || !out) return fail(PINOT_AMD_EINVAL, "execute: bad arguments");
-  std::vector<pinot_amd_segment*> segs(segs_in, segs_in + n);
-  for (auto* s : segs)
-    if (!s) return fail(PINOT_AMD_EINVAL, "execute: null segment");
-  const std::string plan_key = plan_identity(*qq, segs, filter_only);
-  if (pinot_amd_result* hit = plan_cache_take(plan_key)) {  // a prepared plan of this identity: run it
-    std::unique_ptr<pinot_amd_result> hold(hit);
-    hit->stream = (hipStream_t)stream;
-    PlanClock clk(&hit->plan_timing);
-    clk.mark("plan_cache");
-    if (int rc = run_plan(hit)) return rc;
-    clk.mark("launch");
-    *out = hold.release();
-    return 0;
-  }
-  const size_t alloc0 = g_tl_alloc_bytes;
-  auto res = std::make_unique<pinot_amd_result>();
-  pinot_amd_result* r = res.get();
-  r->stream = (hipStream_t)stream;
-  r->plan_key = plan_key;
-  for (auto* sg : segs) r->plan_uids.push_back(sg->uid);
-  PlanClock clk(&r->plan_timing);
-  pinot_amd_query filter_q;
-  if (filter_only) filter_q.preds = qq->preds;  // FilterPlanNode only: no projection, no aggregation
-  const pinot_amd_query* Qp = filter_only ? &filter_q : qq;
+                        bool filter_only, pinot_amd_result** out);
+
+namespace {
+
+// accumulator request of the planner: the slot(s) and expression it reads, its operation and NaN rule
+struct AccReq { int slot; int op; int expr; int slot2; int nan_skip; };
+
+// bytes per row a column's forward index holds
+double slot_bpr(const DevColumn& c) {
+  return c.enc == ENC_FIXED_BIT ? c.bits / 8.0 : c.enc == ENC_RAW ? (double)value_size(c.type) : 0.0;
+}
+// bytes per row a streaming kernel reads of a column: the packed twin's planes where the launch uses it
+double stream_bpr(const DevColumn& c, bool packed) {
+  return packed ? (c.for_lo_bits + c.for_hi_bits) / 8.0 : slot_bpr(c);
+}
+
+// one launch while PlanBuild::plan_launch shapes it
+struct LaunchBuild {
+  size_t li;
+  Launch& L;
+  std::vector<DevSegment> ls;    // the launch's segments (tile_begin / key_seg set)
+  std::vector<uint64_t*> lbits;  // filter-only: their result bitsets
+  int64_t tiles = 0;
+  JitPlan jp;                    // the launch's kernel shape
+};
+
+// What more than one planning phase of execute_impl reads or writes. execute_impl calls the phases in the order
+// they are declared; each returns the usual error code.
+struct PlanBuild {
+  // inputs
+  pinot_amd_query* qq = nullptr;
+  std::vector<pinot_amd_segment*> segs;
+  int32_t n = 0;
+  void* stream = nullptr;
+  bool filter_only = false;
+  pinot_amd_result* r = nullptr;
+  // the effective query (raw_keys)
+  pinot_amd_query filter_q;  // FilterPlanNode only: no projection, no aggregation
   pinot_amd_query raw_gb_q;  // group-by columns redirected to the derived dictionary of raw columns
+  const pinot_amd_query* Qp = nullptr;
+  // slots and leaves (leaves)
+  std::vector<std::string> slot_cols;
+  int nslots = 0;
+  size_t np = 0;
+  std::vector<std::vector<DevLeaf>> seg_leaves;
+  std::vector<int> pred_slot;
+  std::vector<size_t> order;
+  int nclauses = 0;
+  // key space, trims (keys_probe)
+  double dense_keys = 1;
+  std::vector<int64_t> seg_matched, seg_bound;
+  bool limit_possible = false, seg_trim = false, segsel_unsafe = false;
+  int64_t segsel_unsafe_keep = 0;
+  // accumulators (accs, plan_kind)
+  std::vector<AccReq> acc_req;
+  int nacc = 1;
+  std::vector<JitPlan::OrdCol> seg_ord;
+  int64_t num_keys = 0;
+  // batches and device segments (hash_sizes, dev_segs)
+  std::vector<int> seg_batch;
+  std::vector<DevSegment> hsegs;
+  bool packed_on = false;
+  std::vector<uint64_t*> bitset_ptrs;
+  // plan-level kernel choices (kernel_choices, select_plan)
+  int lds_max = 0, cus = 256;
+  JitPlan base;
+  int64_t all_tiles = 0, all_docs = 0;
+  int64_t lds_bytes = 0, hash_lds_bytes = 0;
+  std::vector<int64_t> part_vbase;  // partitioned plans: integer record fields' bases (DevPartition::vbase)
+  std::vector<bool> leaf_slot, value_slot;
+  // launches (group_launches, plan_launches) and the running maxima that size the shared work buffers
+  bool generic_bits = false;
+  std::vector<int32_t> key_seg;
+  size_t nl = 0;
+  size_t max_count_cells = 0, max_rec = 0, max_slab = 0, max_slab_docs = 0;
+  int64_t max_sel = 0;  // selection-vector entries of the largest select launch
+
+  int slot_of(const std::string& name);
+  int probe_matched();
+  void admit_prefixes();
+  int push_acc(const AccReq& rq);
+  void set_narrow(__int128 docs_bound);
+  int64_t lds_arrays();
+
+  int raw_keys();
+  int leaves();
+  int keys_probe();
+  int accs();
+  int plan_kind();
+  int hash_sizes();
+  int dev_segs();
+  int kernel_choices();
+  int select_plan();
+  int group_launches();
+  int plan_launches();
+  int alloc_buffers();
+
+  int plan_launch(size_t li);
+  int launch_segments(LaunchBuild& lb);
+  int launch_shape(LaunchBuild& lb);
+  int launch_helper_passes(LaunchBuild& lb);
+  int launch_partitioned(LaunchBuild& lb);
+  int launch_select(LaunchBuild& lb);
+};
+
+// the query the plan is built for: the filter alone (FilterPlanNode), or the query with raw GROUP BY columns
+// redirected to their derived dictionaries
+int PlanBuild::raw_keys() {
+  if (filter_only) filter_q.preds = qq->preds;  // FilterPlanNode only: no projection, no aggregation
+  Qp = filter_only ? &filter_q : qq;
   for (size_t j = 0; j < Qp->group_by.size(); ++j) {
     const std::string g = Qp->group_by[j];  // a copy: the redirect below rewrites Qp->group_by[j]
     int nraw = 0;
@@ -3078,17 +3065,20 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
     for (auto* s : segs)
       if (int rc = derive_raw_group_dictionary(s, g, &raw_gb_q.group_by[j])) return rc;
   }
-  const pinot_amd_query& Q = *Qp;
+  return 0;
+}
 
-  clk.mark("raw_keys");
+// the slot of a column the kernel must decode (added on first use)
+int PlanBuild::slot_of(const std::string& name) {
+  for (size_t i = 0; i < slot_cols.size(); ++i)
+    if (slot_cols[i] == name) return (int)i;
+  slot_cols.push_back(name);
+  return (int)slot_cols.size() - 1;
+}
+
+int PlanBuild::leaves() {
+  const pinot_amd_query& Q = *Qp;
   // ---- slots: columns the kernel must decode ----
-  std::vector<std::string> slot_cols;
-  auto slot_of = [&](const std::string& name) -> int {
-    for (size_t i = 0; i < slot_cols.size(); ++i)
-      if (slot_cols[i] == name) return (int)i;
-    slot_cols.push_back(name);
-    return (int)slot_cols.size() - 1;
-  };
   for (auto* s : segs) {
     auto need = [&](const std::string& col) -> int {
       if (!s->cols.count(col)) return fail(PINOT_AMD_EINVAL, "segment %s has no column %s", s->name.c_str(), col.c_str());
@@ -3115,10 +3105,10 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
   }
 
   // ---- per-segment leaves (PredicateEvaluatorProvider per segment) ----
-  const size_t np = Q.preds.size();
-  std::vector<std::vector<DevLeaf>> seg_leaves(n, std::vector<DevLeaf>(np));
+  np = Q.preds.size();
+  seg_leaves.assign(n, std::vector<DevLeaf>(np));
   std::vector<std::vector<int>> leaf_slot_col(n, std::vector<int>(np, -1));
-  int nclauses = 0;
+  nclauses = 0;
   for (size_t pi = 0; pi < np; ++pi) nclauses = std::max(nclauses, Q.preds[pi].clause + 1);
   // per predicate, once: whether its column is decoded anyway, and its leaf-cache key (the same on every segment)
   std::vector<char> pred_decoded(np, 0);
@@ -3130,7 +3120,6 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
     pred_decoded[pi] = d ? 1 : 0;
     pred_key[pi] = leaf_cache_key(p, -1, d);
   }
-  const bool leaf_cache = !env_is("PINOT_AMD_LEAF_CACHE", "0");
   for (int si = 0; si < n; ++si) {
     for (size_t pi = 0; pi < np; ++pi) {
       const PredSpec& p = Q.preds[pi];
@@ -3138,14 +3127,14 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
       bool needs_slot = false;
       const bool decoded_anyway = pred_decoded[pi] != 0;
       int rc = make_leaf_for_segment(r, si, segs[si], p, c, -1, &seg_leaves[si][pi], &needs_slot, r->stream,
-                                     decoded_anyway, leaf_cache ? &pred_key[pi] : nullptr);
+                                     decoded_anyway, pred_key[pi]);
       if (rc) return rc;
       if (needs_slot) leaf_slot_col[si][pi] = slot_of(p.column);
     }
   }
   if ((int)slot_cols.size() > kMaxSlots)
     return fail(PINOT_AMD_EUNSUPPORTED, "query reads %zu columns (max %d)", slot_cols.size(), kMaxSlots);
-  const int nslots = (int)slot_cols.size();
+  nslots = (int)slot_cols.size();
   for (int sl = 0; sl < nslots; ++sl)
     for (auto* s : segs)
       if (s->cols.at(slot_cols[sl])->type != segs[0]->cols.at(slot_cols[sl])->type)
@@ -3153,11 +3142,10 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
   // leaf order is the same for all segments: leaves grouped by the slot they read where some segment
   // reads one, slot-less predicates last (segments where such a leaf resolved slot-less keep its
   // CONST/DOC kind, which ignores the values)
-  std::vector<int> pred_slot(np, -1);
+  pred_slot.assign(np, -1);
   for (size_t pi = 0; pi < np; ++pi)
     for (int si = 0; si < n; ++si)
       if (leaf_slot_col[si][pi] >= 0) pred_slot[pi] = leaf_slot_col[si][pi];
-  std::vector<size_t> order;
   for (int sl = 0; sl < nslots; ++sl)
     for (size_t pi = 0; pi < np; ++pi)
       if (pred_slot[pi] == sl) order.push_back(pi);
@@ -3166,8 +3154,73 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
 
   DevQuery& q = r->q;
   memset(&q, 0, sizeof(q));
+  return 0;
+}
 
-  clk.mark("leaves");
+  // Matching docs per segment, counted once at plan time by a filter-only pass when a planning decision
+  // needs them (numGroupsLimit trimming, the selection-vector plan); segments are immutable, so the
+  // counts hold for every re-execution of the plan.
+int PlanBuild::probe_matched() {
+  const pinot_amd_query& Q = *Qp;
+  if (!seg_matched.empty()) return 0;
+  // counts cached on the segments (immutable) by an earlier probe of the same filter; the rest probed
+  const std::string sig = preds_signature(Q.preds);
+  seg_matched.assign(n, -1);
+  std::vector<pinot_amd_segment*> todo;
+  std::vector<int> todo_idx;
+  std::unique_lock<std::mutex> lk(g_match_mu);
+  for (int si = 0; si < n; ++si) {
+    auto it = segs[si]->match_cache.find(sig);
+    if (it != segs[si]->match_cache.end()) {
+      seg_matched[si] = it->second;
+    } else {
+      todo.push_back(segs[si]);
+      todo_idx.push_back(si);
+    }
+  }
+  lk.unlock();
+  if (todo.empty()) return 0;
+  pinot_amd_query fq;
+  fq.preds = Q.preds;
+  pinot_amd_result* fr = nullptr;
+  if (int rc = execute_impl(&fq, todo.data(), (int32_t)todo.size(), stream, true, &fr)) return rc;
+  std::unique_ptr<pinot_amd_result> hold(fr);
+  for (size_t k = 0; k < todo.size(); ++k) {
+    int64_t c = 0;
+    if (int rc = pinot_amd_bitset_count((const uint64_t*)fr->bitsets[k]->p, todo[k]->num_docs, &c, stream)) return rc;
+    seg_matched[todo_idx[k]] = c;
+    std::lock_guard<std::mutex> g(g_match_mu);
+    todo[k]->match_cache[sig] = c;
+  }
+  return 0;
+}
+
+  // admission prefixes (dense trimming): the docs of segment si that should hold numGroupsLimit distinct
+  // keys, twice the coupon-collector expectation for K uniform keys (K ln(K / (K - L)) matching docs,
+  // scaled by the segment's selectivity) plus 64 Ki docs; a segment that cannot reach the limit needs
+  // no pass (everything admitted). A prefix that still sees fewer keys is redone over the whole segment.
+void PlanBuild::admit_prefixes() {
+  const pinot_amd_query& Q = *Qp;
+  r->a_prefix.assign(n, 0);
+  r->a_docs.assign(n, 0);
+  for (int si = 0; si < n; ++si) {
+    const int64_t nd = segs[si]->num_docs;
+    r->a_docs[si] = nd;
+    if (seg_bound[si] < Q.num_groups_limit) continue;
+    double ks = 1;
+    for (auto& g : Q.group_by) ks *= (double)std::max(segs[si]->cols.at(g)->card, 1);
+    const double L = (double)Q.num_groups_limit;
+    const double need = ks > L ? ks * std::log(ks / (ks - L)) : (double)nd;
+    const double sel = (!seg_matched.empty() && nd > 0) ? std::max((double)seg_matched[si] / (double)nd, 1e-9) : 1.0;
+    const double rows = 2.0 * need / sel + 65536.0;
+    int64_t pfx = rows >= (double)nd ? nd : ((int64_t)rows + kTileDocs - 1) / kTileDocs * kTileDocs;
+    if (const char* e = knob("PINOT_AMD_ADMIT_PREFIX")) pfx = std::min<int64_t>(nd, std::max<int64_t>(kTileDocs, atoll(e)));
+    r->a_prefix[si] = std::min(pfx, nd);
+  }
+}
+
+int PlanBuild::keys_probe() {
+  const pinot_amd_query& Q = *Qp;
   // ---- group-by key space: merged dictionaries (union over the batch, dictionary order) ----
   r->num_group_by = (int32_t)Q.group_by.size();
   r->limit = Q.num_groups_limit;
@@ -3186,7 +3239,7 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
     }
     r->srv_safe = only_keys && std::all_of(seen.begin(), seen.end(), [](bool b) { return b; });
   }
-  double dense_keys = 1;
+  dense_keys = 1;
   for (size_t j = 0; j < Q.group_by.size(); ++j) {
     const std::string& g = Q.group_by[j];
     std::shared_ptr<const MergedKeyColumn> m;
@@ -3224,47 +3277,10 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
     dense_keys *= (double)std::max<size_t>(m->size(), 1);
     r->keys.push_back(std::move(m));
   }
-  // Matching docs per segment, counted once at plan time by a filter-only pass when a planning decision
-  // needs them (numGroupsLimit trimming, the selection-vector plan); segments are immutable, so the
-  // counts hold for every re-execution of the plan.
-  std::vector<int64_t> seg_matched;
-  auto probe_matched = [&]() -> int {
-    if (!seg_matched.empty()) return 0;
-    // counts cached on the segments (immutable) by an earlier probe of the same filter; the rest probed
-    const std::string sig = preds_signature(Q.preds);
-    seg_matched.assign(n, -1);
-    std::vector<pinot_amd_segment*> todo;
-    std::vector<int> todo_idx;
-    std::unique_lock<std::mutex> lk(g_match_mu);
-    for (int si = 0; si < n; ++si) {
-      auto it = segs[si]->match_cache.find(sig);
-      if (it != segs[si]->match_cache.end()) {
-        seg_matched[si] = it->second;
-      } else {
-        todo.push_back(segs[si]);
-        todo_idx.push_back(si);
-      }
-    }
-    lk.unlock();
-    if (todo.empty()) return 0;
-    pinot_amd_query fq;
-    fq.preds = Q.preds;
-    pinot_amd_result* fr = nullptr;
-    if (int rc = execute_impl(&fq, todo.data(), (int32_t)todo.size(), stream, true, &fr)) return rc;
-    std::unique_ptr<pinot_amd_result> hold(fr);
-    for (size_t k = 0; k < todo.size(); ++k) {
-      int64_t c = 0;
-      if (int rc = pinot_amd_bitset_count((const uint64_t*)fr->bitsets[k]->p, todo[k]->num_docs, &c, stream)) return rc;
-      seg_matched[todo_idx[k]] = c;
-      std::lock_guard<std::mutex> g(g_match_mu);
-      todo[k]->match_cache[sig] = c;
-    }
-    return 0;
-  };
   // numGroupsLimit: a segment can only reach the limit if it can hold that many keys (matching docs
   // and its own dictionaries' key space bound it); otherwise no trimming can happen
-  std::vector<int64_t> seg_bound(n, 0);
-  bool limit_possible = false;
+  seg_bound.assign(n, 0);
+  limit_possible = false;
   if (!Q.group_by.empty() && !filter_only) {
     for (int si = 0; si < n; ++si) {
       double b = (double)segs[si]->num_docs;
@@ -3277,7 +3293,7 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
     // The key space alone allows numGroupsLimit groups somewhere: bound each segment by its matching
     // docs too (a segment's groups <= its matching docs). Counted once at plan time by a filter-only
     // pass; segments are immutable, so the counts hold for every re-execution of the plan.
-    if (limit_possible && !Q.preds.empty() && !env_is("PINOT_AMD_TRIM_PROBE", "0")) {
+    if (limit_possible && !Q.preds.empty()) {
       if (int rc = probe_matched()) return rc;
       limit_possible = false;
       for (int si = 0; si < n; ++si) {
@@ -3295,7 +3311,7 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
   // docs whose group ranks within it. A segment that cannot hold more than LIMIT groups trims nothing. (Below
   // the threshold, and with serverReturnFinalResult, the segments trim too, but the LIMIT groups the server
   // keeps are exact either way: server_trim.)
-  bool seg_trim = false;
+  seg_trim = false;
   if (r->srv_safe && r->srv_limit >= 0 && r->srv_limit >= r->srv_sort_threshold && !r->srv_final && !filter_only &&
       !Q.group_by.empty()) {
     auto over = [&]() {
@@ -3307,18 +3323,14 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
       if (int rc = probe_matched()) return rc;
       for (int si = 0; si < n; ++si) seg_bound[si] = std::min(seg_bound[si], seg_matched[si]);
     }
-    seg_trim = over() && !env_is("PINOT_AMD_SEG_TRIM", "0");
-    if (over() && !seg_trim)
-      return fail(PINOT_AMD_EUNSUPPORTED, "server result limit: a segment-level safe trim (ORDER BY = GROUP BY, "
-                                          "LIMIT %lld >= sortAggregateLimitThreshold %lld) disabled by PINOT_AMD_SEG_TRIM=0",
-                  (long long)r->srv_limit, (long long)r->srv_sort_threshold);
+    seg_trim = over();
   }
   // Unsafe trim (ORDER BY other than the GROUP BY keys) with minSegmentGroupTrimSize > 0: each segment keeps its top
   // max(minSegmentGroupTrimSize, 5 x LIMIT) groups by the ORDER BY, aggregation values included (QueryContext.java:
   // 575-578, GroupByUtils.getTableCapacity, GroupByOperator.java:157-175): the (key, segment) hash plan with the
   // per-segment selection (segsel) when some segment could hold more.
-  bool segsel_unsafe = false;
-  int64_t segsel_unsafe_keep = 0;
+  segsel_unsafe = false;
+  segsel_unsafe_keep = 0;
   if (!r->srv_safe && !r->srv_order.empty() && Q.min_seg_trim > 0 && r->srv_limit >= 0 && !filter_only &&
       !Q.group_by.empty()) {
     const int64_t seg_keep = std::max<int64_t>(Q.min_seg_trim, 5 * r->srv_limit);
@@ -3332,34 +3344,23 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
     segsel_unsafe = over;
     segsel_unsafe_keep = seg_keep;
   }
-  // admission prefixes (dense trimming): the docs of segment si that should hold numGroupsLimit distinct
-  // keys, twice the coupon-collector expectation for K uniform keys (K ln(K / (K - L)) matching docs,
-  // scaled by the segment's selectivity) plus 64 Ki docs; a segment that cannot reach the limit needs
-  // no pass (everything admitted). A prefix that still sees fewer keys is redone over the whole segment.
-  auto admit_prefixes = [&]() {
-    r->a_prefix.assign(n, 0);
-    r->a_docs.assign(n, 0);
-    for (int si = 0; si < n; ++si) {
-      const int64_t nd = segs[si]->num_docs;
-      r->a_docs[si] = nd;
-      if (seg_bound[si] < Q.num_groups_limit) continue;
-      double ks = 1;
-      for (auto& g : Q.group_by) ks *= (double)std::max(segs[si]->cols.at(g)->card, 1);
-      const double L = (double)Q.num_groups_limit;
-      const double need = ks > L ? ks * std::log(ks / (ks - L)) : (double)nd;
-      const double sel = (!seg_matched.empty() && nd > 0) ? std::max((double)seg_matched[si] / (double)nd, 1e-9) : 1.0;
-      const double rows = 2.0 * need / sel + 65536.0;
-      int64_t pfx = rows >= (double)nd ? nd : ((int64_t)rows + kTileDocs - 1) / kTileDocs * kTileDocs;
-      if (const char* e = knob("PINOT_AMD_ADMIT_PREFIX")) pfx = std::min<int64_t>(nd, std::max<int64_t>(kTileDocs, atoll(e)));
-      r->a_prefix[si] = std::min(pfx, nd);
-    }
-  };
+  return 0;
+}
 
-  clk.mark("keys_probe");
+int PlanBuild::push_acc(const AccReq& rq) {
+  DevQuery& q = r->q;
+  if (nacc >= kMaxAcc) return fail(PINOT_AMD_EUNSUPPORTED, "too many aggregations");
+  acc_req[nacc] = rq;
+  q.acc_op[nacc++] = rq.op;
+  return 0;
+}
+
+int PlanBuild::accs() {
+  const pinot_amd_query& Q = *Qp;
+  DevQuery& q = r->q;
   // ---- accumulators: acc 0 = COUNT; others grouped by slot; ACC_FIRST_DOC last ----
   // nan_skip: MinMaxRangePair.apply compares with < / >, so NaN never enters the pair (MIN / MAX of
   // an aggregation-only query propagate it like Math.min / Math.max)
-  struct AccReq { int slot; int op; int expr; int slot2; int nan_skip; };
   std::vector<AccReq> reqs;
   std::vector<int> agg_req(Q.aggs.size(), -1), agg_req2(Q.aggs.size(), -1);
   auto find_req = [&](const AccReq& rq) -> int {
@@ -3404,15 +3405,9 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
     }
   }
   std::vector<int> req_acc(reqs.size());
-  std::vector<AccReq> acc_req(kMaxAcc + 2, AccReq{0, 0, 0, -1, 0});
-  int nacc = 1;
+  acc_req.assign(kMaxAcc + 2, AccReq{0, 0, 0, -1, 0});
+  nacc = 1;
   q.acc_op[0] = ACC_COUNT;
-  auto push_acc = [&](const AccReq& rq) -> int {
-    if (nacc >= kMaxAcc) return fail(PINOT_AMD_EUNSUPPORTED, "too many aggregations");
-    acc_req[nacc] = rq;
-    q.acc_op[nacc++] = rq.op;
-    return 0;
-  };
   for (int sl = 0; sl < kMaxSlots; ++sl)
     for (size_t k = 0; k < reqs.size(); ++k)
       if (reqs[k].slot == sl) {
@@ -3426,8 +3421,12 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
     r->agg_acc.push_back(agg_req[ai] < 0 ? 0 : req_acc[agg_req[ai]]);
     r->agg_acc2.push_back(agg_req2[ai] < 0 ? 0 : req_acc[agg_req2[ai]]);
   }
+  return 0;
+}
 
-  clk.mark("accs");
+int PlanBuild::plan_kind() {
+  const pinot_amd_query& Q = *Qp;
+  DevQuery& q = r->q;
   // ---- plan kind ----
   // dense table: mixed-radix keys over the merged dictionaries; hash table: key spaces beyond the
   // dense cap (DictionaryBasedGroupKeyGenerator's Int/Long/ArrayMapBasedHolder) and numGroupsLimit
@@ -3469,7 +3468,6 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
     r->admit = false;
   }
   if (r->admit) admit_prefixes();
-  std::vector<JitPlan::OrdCol> seg_ord;
   if (seg_trim) {
     // ORDER BY rank of a dense key: the first ORDER BY column most significant, DESC columns flipped
     std::vector<std::pair<int, int>> ocols;  // (group column, ascending), first occurrence of each column
@@ -3493,13 +3491,16 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
   }
   q.nacc = (Q.aggs.empty() && Q.group_by.empty()) ? 0 : nacc;  // filter-only: count matches
   if (filter_only) q.nacc = 0;
-  const int64_t num_keys = r->kind == PLAN_HASH ? 0 : (int64_t)dense_keys;
+  num_keys = r->kind == PLAN_HASH ? 0 : (int64_t)dense_keys;
   q.num_keys = num_keys;
+  return 0;
+}
 
-  clk.mark("plan_kind");
+int PlanBuild::hash_sizes() {
+  const pinot_amd_query& Q = *Qp;
   // ---- hash plans: key packing and table sizes ----
   const int64_t table_budget = env_i64("PINOT_AMD_HASH_TABLE_BYTES", (int64_t)4 << 30);  // per trim scan table
-  std::vector<int> seg_batch(n, 0);
+  seg_batch.assign(n, 0);
   if (r->kind == PLAN_HASH) {
     std::vector<int64_t> sizes;
     for (auto& m : r->keys) sizes.push_back((int64_t)std::max<size_t>(m->size(), 1));
@@ -3628,11 +3629,14 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
         if ((double)c < 2.0 * 1) return fail(PINOT_AMD_EINVAL, "internal: empty trim batch");
     }
   }
+  return 0;
+}
 
-  clk.mark("hash_sizes");
+int PlanBuild::dev_segs() {
+  const pinot_amd_query& Q = *Qp;
   // ---- device segments (one DevSegment per segment; tile_begin / key_seg set per launch) ----
-  std::vector<DevSegment> hsegs(n);
-  const bool packed_on = packed_enabled();
+  hsegs.assign(n, DevSegment());
+  packed_on = packed_enabled();
   r->slot_names = slot_cols;
   for (int si = 0; si < n; ++si) {
     DevSegment& ds = hsegs[si];
@@ -3696,7 +3700,7 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
     r->expand_total = items;
     if (int rc = r->d_expand_jobs.alloc_copy(jobs.data(), jobs.size() * sizeof(ExpandJob), 0)) return rc;
   }
-  std::vector<uint64_t*> bitset_ptrs(n, nullptr);
+  bitset_ptrs.assign(n, nullptr);
   if (filter_only) {
     for (int si = 0; si < n; ++si) {
       const int64_t words = std::max<int64_t>((segs[si]->num_docs + kTileDocs - 1) / kTileDocs, 1) * (kTileDocs / 64);
@@ -3708,17 +3712,36 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
       r->bitsets.push_back(std::move(b));
     }
   }
+  return 0;
+}
 
-  clk.mark("dev_segs");
+// JitAcc::narrow of every integer SUM: whether |value| x docs_bound fits int64
+void PlanBuild::set_narrow(__int128 docs_bound) {
+  for (JitAcc& a : base.accs) {
+    a.narrow = 0;
+    if (a.op != ACC_SUM_I128 || env_is("PINOT_AMD_NARROW_SUMS", "0")) continue;
+    const __int128 m = acc_maxabs(segs, slot_cols, a);
+    a.narrow = (m >= 0 && m * docs_bound <= (__int128)INT64_MAX) ? 1 : 0;
+  }
+}
+
+int64_t PlanBuild::lds_arrays() {
+  int k = 0;
+  jit_lds_layout(base, &k);
+  return (int64_t)k;
+}
+
+int PlanBuild::kernel_choices() {
+  const pinot_amd_query& Q = *Qp;
+  DevQuery& q = r->q;
   // ---- plan-level kernel choices (shared by every launch) ----
-  int lds_max = 0;
+  lds_max = 0;
   {
     int dev = 0;
     HIP_OK(hipGetDevice(&dev));
     if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) lds_max = 65536;
     lds_max = std::min(lds_max, 160 * 1024);
   }
-  JitPlan base;
   base.nclauses = nclauses;
   for (size_t j = 0; j < Q.group_by.size(); ++j) {
     base.group.push_back({slot_of(Q.group_by[j]), r->kind == PLAN_HASH ? 0 : r->key_stride[j]});
@@ -3731,7 +3754,7 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
   base.seg_ord = seg_ord;
   base.bitset = filter_only;
   base.aggregate = q.nacc > 0;
-  int cus = 256;
+  cus = 256;
   {
     int dev = 0;
     HIP_OK(hipGetDevice(&dev));
@@ -3741,42 +3764,13 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
   // block adds) < 2^63 for every segment: a scan block owns ceil(tiles / grid) tiles with grid >=
   // min(CUs, tiles / kPartSub); a partition aggregation block ceil(records / agg_grid) <= ceil(docs /
   // CUs) records. Bounded with the whole batch, so every launch of the plan satisfies it.
-  int64_t all_tiles = 0, all_docs = 0;
+  all_tiles = 0, all_docs = 0;
   for (auto* s : segs) {
     all_tiles += (s->num_docs + kTileDocs - 1) / kTileDocs;
     all_docs += s->num_docs;
   }
-  auto set_narrow = [&](__int128 docs_bound) {
-    auto maxabs = [&](int sl) -> __int128 {
-      __int128 m = 0;
-      for (auto* s : segs) {
-        const Column& c = *s->cols.at(slot_cols[sl]);
-        if (!c.has_range) return -1;
-        const __int128 a = c.vmax < 0 ? -(__int128)c.vmax : (__int128)c.vmax;
-        const __int128 b = c.vmin < 0 ? -(__int128)c.vmin : (__int128)c.vmin;
-        m = std::max(m, std::max(a, b));
-      }
-      return m;
-    };
-    for (JitAcc& a : base.accs) {
-      a.narrow = 0;
-      if (a.op != ACC_SUM_I128 || env_is("PINOT_AMD_NARROW_SUMS", "0")) continue;
-      __int128 m = maxabs(a.slot);
-      if (m >= 0 && a.expr != EXPR_COL) {
-        const __int128 m2 = maxabs(a.slot2);
-        m = m2 < 0 ? -1 : a.expr == EXPR_MUL ? m * m2 : m + m2;
-      }
-      a.narrow = (m >= 0 && m * docs_bound <= (__int128)INT64_MAX) ? 1 : 0;
-    }
-  };
-  auto lds_arrays = [&]() {
-    int k = 0;
-    jit_lds_layout(base, &k);
-    return (int64_t)k;
-  };
-  int64_t lds_bytes = (int64_t)q.nacc * std::max<int64_t>(num_keys, 1) * 8;
-  int64_t hash_lds_bytes = 0;  // hash plans: the LDS first level (JitPlan::hash_lds)
-  std::vector<int64_t> part_vbase;  // partitioned plans: integer record fields' bases (DevPartition::vbase)
+  lds_bytes = (int64_t)q.nacc * std::max<int64_t>(num_keys, 1) * 8;
+  hash_lds_bytes = 0;  // hash plans: the LDS first level (JitPlan::hash_lds)
   if (r->kind == PLAN_DENSE && q.nacc > 0) {
     const int64_t min_grid = std::max<int64_t>(1, std::min<int64_t>(cus, all_tiles / kPartSub));
     set_narrow((__int128)((all_tiles + min_grid - 1) / min_grid) * kTileDocs);
@@ -3873,15 +3867,20 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
     base.hash_words = r->nw + (r->trim ? 1 : 0);
     for (size_t j = 0; j < Q.group_by.size(); ++j) base.hash_pack.push_back({r->pack_word[j], r->pack_shift[j]});
   }
+  return 0;
+}
 
-  clk.mark("kernel_choices");
+int PlanBuild::select_plan() {
+  const pinot_amd_query& Q = *Qp;
+  DevQuery& q = r->q;
   // ---- selection-vector plan (late materialisation) ----
   // A selective filter over narrow rows: the select pass reads only the filter columns and appends the
   // matching docIds; the gather pass reads the group-by / aggregated columns of those docs only (64 B
   // sectors at random positions). Chosen when its bytes, from the exact per-segment match counts,
   // undercut the fused scan's: filter columns + 16 B per match (vector write + read) + the value columns'
   // sectors a match touches + a per-match gather cost, against every column of every doc.
-  std::vector<bool> leaf_slot(nslots, false), value_slot(nslots, false);
+  leaf_slot.assign(nslots, false);
+  value_slot.assign(nslots, false);
   for (size_t pi = 0; pi < np; ++pi)
     if (pred_slot[pi] >= 0) leaf_slot[pred_slot[pi]] = true;
   for (auto& g : base.group) value_slot[g.first] = true;
@@ -3890,13 +3889,6 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
       value_slot[a.slot] = true;
       if (a.expr != EXPR_COL) value_slot[a.slot2] = true;
     }
-  auto slot_bpr = [](const DevColumn& c) -> double {
-    return c.enc == ENC_FIXED_BIT ? c.bits / 8.0 : c.enc == ENC_RAW ? (double)value_size(c.type) : 0.0;
-  };
-  // bytes per row a streaming kernel reads of a column: the packed twin's planes where the launch uses it
-  auto stream_bpr = [&](const DevColumn& c, bool packed) -> double {
-    return packed ? (c.for_lo_bits + c.for_hi_bits) / 8.0 : slot_bpr(c);
-  };
   const char* sel_env = knob("PINOT_AMD_SELECT");
   // (a partitioned plan qualifies too: when its filter keeps few docs, the gather adds them straight into
   // the HBM table, where the partitioned plan would hand over to a fused direct-atomic scan of every row)
@@ -3964,8 +3956,8 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
       }
       const double sel_t = std::max(leaf_b / kBw, docs_all * sel_doc) + matches * kGatherDoc + (sel_bytes - leaf_b) / kBw;
       base.select = forced || sel_t < 0.9 * scan_t;
-      base.word_select = base.select && wordy && !env_is("PINOT_AMD_WORD_SELECT", "0");
-      base.wsel_words = (int)env_i64("PINOT_AMD_WSEL_WORDS", 4) == 8 ? 8 : 4;  // swept: 8 is 4 % faster at 0.01-0.1 %, 2 % slower at 1 %
+      // (4 words per lane and step; swept: 8 is 4 % faster at 0.01-0.1 %, 2 % slower at 1 %)
+      base.word_select = base.select && wordy;
       if (base.select && base.partitioned) {  // the gather aggregates into the dense HBM table
         r->kind = PLAN_DENSE;
         base.partitioned = false;
@@ -4113,11 +4105,13 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
       for (JitAcc& a : base.accs) a.narrow = 0;
     }
   }
+  return 0;
+}
 
-  clk.mark("select_plan");
+int PlanBuild::group_launches() {
   // ---- launches: segments of a batch grouped by shape (slot encodings and fixed-bit widths) ----
-  const bool generic_bits = env_is("PINOT_AMD_GENERIC_BITS", "1");
-  std::vector<int32_t> key_seg(n, 0);
+  generic_bits = env_is("PINOT_AMD_GENERIC_BITS", "1");
+  key_seg.assign(n, 0);
   {
     std::vector<int32_t> cnt(r->nbatches, 0);
     for (int si = 0; si < n; ++si) key_seg[si] = cnt[seg_batch[si]]++;
@@ -4198,6 +4192,484 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
       }
     }
   }
+  return 0;
+}
+
+// a launch's segment descriptors (tile ranges, key_seg), its query block and, for a word-level select of few
+// matching docs, the fused inverted-index expansion
+int PlanBuild::launch_segments(LaunchBuild& lb) {
+  DevQuery& q = r->q;
+  Launch& L = lb.L;
+  std::vector<DevSegment>& ls = lb.ls;
+  std::vector<uint64_t*>& lbits = lb.lbits;
+  int64_t& tiles = lb.tiles;
+  for (int si : L.segs) {
+    DevSegment ds = hsegs[si];
+    ds.tile_begin = tiles;
+    ds.key_seg = r->admit ? si : key_seg[si];
+    ds.pad = r->admit ? 1 : 0;  // sequential admission over whole segments: each one walked to its end
+    // (a tile-level select with G tiles per step: the segment's range padded to a multiple of G; the
+    // padding tiles match nothing and read only their columns' staging padding)
+    const int64_t G = base.sel_group;
+    tiles += ((segs[si]->num_docs + kTileDocs - 1) / kTileDocs + G - 1) / G * G;
+    L.docs += segs[si]->num_docs;
+    ls.push_back(ds);
+    lbits.push_back(bitset_ptrs[si]);
+  }
+  L.tiles = tiles;
+  L.q = q;
+  L.q.nsegs = (int32_t)L.segs.size();
+  L.q.total_tiles = tiles;
+  if (int rc = L.d_segs.alloc_copy(ls.data(), ls.size() * sizeof(DevSegment), 0)) return rc;
+  static_assert(sizeof(DevSegment) % 8 == 0, "the count pass checksums descriptors in 8-byte words");
+  L.h_segs = ls;
+  // fused when few docs match (measured: 0.01 % / 0.1 % of 1B rows 0.36 / 0.52 -> 0.24 / 0.42 ms; at
+  // 1 % the separate expansion's occupancy wins, 1.08 vs 1.17 ms); PINOT_AMD_FUSED_INV_SELECT=1 forces it
+  double lm = 0, ld = 0;
+  for (int si : L.segs) {
+    lm += seg_matched.empty() ? 0.0 : (double)seg_matched[si];
+    ld += (double)segs[si]->num_docs;
+  }
+  const bool fuse = env_is("PINOT_AMD_FUSED_INV_SELECT", "1") ||
+                    (!env_is("PINOT_AMD_FUSED_INV_SELECT", "0") && !seg_matched.empty() && lm <= 0.004 * ld);
+  if (base.word_select && fuse) {
+    // the launch's segments as work items of G-chunk groups; each inverted-index leaf mapped to its
+    // expansion job (its DevLeaf::bits is the job's bitset buffer)
+    const int G = expand_group();
+    std::vector<FusedSelSeg> fv(ls.size());
+    int64_t items = 0;
+    bool ok = true, neg_bits = false;
+    for (size_t k = 0; k < ls.size(); ++k) {
+      FusedSelSeg& f = fv[k];
+      memset(&f, 0, sizeof(f));
+      f.item_begin = items;
+      f.seg = (int32_t)k;
+      const int64_t words = (segs[L.segs[k]]->num_docs + kTileDocs - 1) / kTileDocs * (kTileDocs / 64);
+      f.nitems = (int32_t)((words + 1024 * G - 1) / (1024 * G));
+      for (int j = 0; j < kMaxLeaves; ++j) f.job[j] = -1;
+      for (size_t j = 0; j < order.size(); ++j) {
+        if (ls[k].leaves[j].kind != LEAF_DOC_BITSET) continue;
+        for (size_t ii = 0; ii < r->inv_leaves.size(); ++ii)
+          if (r->inv_leaves[ii].bitset->p == (const void*)ls[k].leaves[j].bits) f.job[j] = (int32_t)ii;
+        ok &= f.job[j] >= 0 && r->inv_leaves[f.job[j]].nchunks >= f.nitems;
+        neg_bits |= ls[k].leaves[j].negate != 0;
+      }
+      items += f.nitems;
+    }
+    if (ok) {
+      if (int rc = L.d_fused.alloc_copy(fv.data(), fv.size() * sizeof(FusedSelSeg), 0)) return rc;
+      L.fused = true;
+      L.nfused = (int32_t)fv.size();
+      L.fused_items = items;
+      L.fused_leaves = (int32_t)order.size();
+      // the clause-fold variant measured 5-9 % faster (sweep_inv_fused_variant.txt); negated bitset leaves need
+      // the per-leaf fold
+      L.fused_clause = !neg_bits;
+      L.fused_clauses = base.nclauses;
+    }
+  }
+  if (filter_only)
+    if (int rc = L.d_bitset_ptrs.alloc_copy(lbits.data(), lbits.size() * sizeof(uint64_t*), 0)) return rc;
+  return 0;
+}
+
+// the launch's kernel shape: slots and leaves as the segments of the launch allow, the pipeline depth, the
+// partitioned scatter's staging, and the launch's algorithmic bytes
+int PlanBuild::launch_shape(LaunchBuild& lb) {
+  const pinot_amd_query& Q = *Qp;
+  Launch& L = lb.L;
+  std::vector<DevSegment>& ls = lb.ls;
+  JitPlan& jp = lb.jp;
+  const int64_t tiles = lb.tiles;
+  jp = base;
+  for (int sl = 0; sl < nslots; ++sl) {
+    const int enc = ls[0].cols[sl].enc;
+    JitSlot js{enc, ls[0].cols[sl].type, 0, 0};
+    if (enc != ENC_RAW) {  // dictionary of <= 64 entries everywhere: lane-register table
+      bool small = true;
+      for (auto& d : ls) small &= d.cols[sl].card <= 64 && d.cols[sl].card > 0;
+      js.dict_regs = small ? 1 : 0;
+    }
+    if (enc == ENC_FIXED_BIT) {  // width shared by the launch (<= 15): compile-time shifts
+      js.bits = ls[0].cols[sl].bits;
+      for (auto& d : ls)
+        if (d.cols[sl].bits != js.bits) js.bits = 0;
+      if (js.bits > 15 || generic_bits) js.bits = 0;
+    }
+    if (L.packed >> sl & 1u) {  // the twin's plane widths: the same in every segment of the launch
+      // (a select pass streams the filter columns only; its gather reads the other columns' raw bytes)
+      bool same = enc == ENC_RAW && !(jp.select && !leaf_slot[sl]);
+      for (auto& d : ls)
+        same &= d.cols[sl].for_twin && d.cols[sl].for_lo_bits == ls[0].cols[sl].for_lo_bits &&
+                d.cols[sl].for_hi_bits == ls[0].cols[sl].for_hi_bits;
+      if (same) {
+        js.packed = 1;
+        js.for_lo = ls[0].cols[sl].for_lo_bits;
+        js.for_hi = ls[0].cols[sl].for_hi_bits;
+      } else {
+        L.packed &= ~(1u << sl);
+      }
+    }
+    jp.slots.push_back(js);
+  }
+  for (size_t k = 0; k < order.size(); ++k) {
+    JitLeaf jl{pred_slot[order[k]], Q.preds[order[k]].clause, ls[0].leaves[k].negate, 0u};
+    bool small_sets = jl.slot >= 0;
+    for (auto& d : ls) {
+      jl.kinds |= 1u << d.leaves[k].kind;
+      if (jl.slot >= 0) small_sets &= d.cols[jl.slot].card < 64 * 32;
+    }
+    jl.bits_regs = (small_sets && (jl.kinds & (1u << LEAF_DICT_SET))) ? 1 : 0;
+    // accept masks: a dictionary column of <= 64 values in every segment, leaves that are dictId ranges /
+    // sets / constants (one bit extract per doc instead of a range compare or a set lookup)
+    {
+      const uint32_t ok = (1u << LEAF_DICT_RANGE) | (1u << LEAF_DICT_SET) | (1u << LEAF_CONST);
+      int64_t maxc = 0;
+      bool dict = jl.slot >= 0 && ls[0].cols[jl.slot].enc != ENC_RAW;
+      for (auto& d : ls) if (jl.slot >= 0) maxc = std::max<int64_t>(maxc, d.cols[jl.slot].card);
+      if (dict && !(jl.kinds & ~ok) && (jl.kinds & ((1u << LEAF_DICT_RANGE) | (1u << LEAF_DICT_SET))) && maxc <= 64) {
+        jl.mask = maxc <= 32 ? 1 : 2;
+        jl.bits_regs = 0;
+        // fixed-bit columns of <= 6 bits in 256-thread scan / select blocks: an LDS accept table per
+        // (clause, column) indexed by F = 4, 2 or 1 packed fields (4 / F lookups per lane of 4 docs), the
+        // table at most 2^lut_max bytes (12: 4 KiB, one lookup per 4 docs for <= 3
+        // bits). Tables of <= 2^8 bytes (one dword per LDS bank) never conflict, but the extra lookups
+        // cost more than the ~6 conflict cycles they save: SSB 8.50 -> 8.56 ms at a 2^8 cap
+        // (profiles/r04/sweep_ssb_lut_cap.txt) -- the select pass is latency-bound, not LDS-bound.
+        const JitSlot& js = jp.slots[jl.slot];
+        constexpr int lut_max = 12;
+        if (js.enc == ENC_FIXED_BIT && js.bits >= 1 && js.bits <= 6 && !jp.partitioned &&
+            (jp.scan_nsub == 1 || jp.select))
+          jl.lut = 4 * js.bits <= lut_max ? 4 * js.bits : 2 * js.bits <= lut_max ? 2 * js.bits : js.bits;
+      }
+    }
+    // larger dictId sets (<= 4096 words) are read from LDS, not from global memory per doc, by the
+    // 256-thread blocks of non-partitioned plans (fused scans with nsub 1, every select pass)
+    if (!jl.bits_regs && !jl.mask && jl.slot >= 0 && (jl.kinds & (1u << LEAF_DICT_SET)) && !jp.partitioned &&
+        (jp.scan_nsub == 1 || jp.select)) {
+      int64_t w = 0;
+      for (auto& d : ls) w = std::max<int64_t>(w, (d.cols[jl.slot].card >> 5) + 1);
+      int64_t used = 0;
+      for (auto& o : jp.leaves) used += o.lds_words;
+      w = (w + 3) & ~(int64_t)3;
+      if (w <= 4096 && used + w <= 8192) jl.lds_words = (int)w;
+    }
+    jp.leaves.push_back(jl);
+  }
+  {  // pipeline depth: ~4 KiB in flight per wave (256 docs x bytes per row)
+    double bpr = 0;
+    for (size_t sl = 0; sl < jp.slots.size(); ++sl) {
+      if (jp.select && !leaf_slot[sl]) continue;  // a select pass streams the filter columns only
+      const JitSlot& js = jp.slots[sl];
+      bpr += js.enc == ENC_FIXED_BIT ? (js.bits > 0 ? js.bits : 16) / 8.0
+             : js.packed            ? (js.for_lo + js.for_hi) / 8.0  // the bytes the launch streams
+             : js.enc == ENC_RAW    ? value_size(js.type) : 0.0;
+    }
+    jp.depth = bpr <= 0 ? 1 : (int)std::min(4.0, std::max(1.0, std::ceil(4096.0 / (256.0 * bpr))));
+    // a select step of G tiles loads G tiles per register set: the same bytes in flight with 1/G the sets
+    if (jp.sel_group > 1) jp.depth = std::max(1, (jp.depth + jp.sel_group - 1) / jp.sel_group);
+    if (const char* pd = knob("PINOT_AMD_PREFETCH")) jp.depth = std::max(1, std::min(8, atoi(pd)));
+    // non-temporal column loads for wide-row fused scans (configs[1]: 3.58 -> 3.51 ms per 1B rows); the
+    // narrow SSB select passes measured 1-3 % slower with them, the partitioned scatter 10 % slower
+    // bpr counts the bytes the launch streams (packed twins at their plane widths): configs[1] with twins is
+    // 15.375 B/row and still gains from the hint (2.665 -> 2.588 ms per 1B rows, profiles/r07/sweep_packed.txt),
+    // so the bound sits at 15 B/row; rows between the SSB passes' widths and 15 B were not measured
+    jp.nt_loads = bpr >= 15.0 && !jp.partitioned && !jp.select;
+    // XCD-aware tile ranges where blocks read per-segment tables beside the columns: the admission bitmaps
+    // (128 KiB per segment for configs[3]) thrashed each XCD's L2 when its blocks spanned every segment
+    // (default-limit configs[3] scatter: 20.1 -> 8.8 GB fetched per 400M rows, 4.87 -> 4.15 ms per plan;
+    // profiles/r05/pmc_hcdef_xcd.txt).
+    jp.xcd_remap = jp.admit;
+  }
+  if (jp.partitioned) {
+    jit_layout_records(&jp);
+    // sampled allotments replace the exact count pass once the strided histogram has >= 64 tiles
+    const int64_t stride = env_i64("PINOT_AMD_SAMPLE_STRIDE", 32);
+    jp.part_sampled = stride > 0 && tiles >= 64 * stride;
+    if (jp.part_sampled) L.part.sample_stride = stride;
+    // scatter staging: as many records per partition as the LDS holds (up to 64); below 4 a run is
+    // too short to pay for the staging round trip and records are written directly. A scatter block is
+    // kPartSub 256-thread groups: one CU-wide block per CU with all the LDS for staging
+    // admission plans: the segment's admission bitmap beside the staging (an LDS read per doc instead of a
+    // dependent global load; the scatter writes only the admitted docs' records, so a short staging serves)
+    jp.admit_lds = jp.admit &&
+                   jit_scatter_lds([&] { JitPlan t = jp; t.admit_lds = true; return t; }(), 4) <= (size_t)lds_max;
+    int cap = 64;
+    while (cap >= 4 && jit_scatter_lds(jp, cap) > (size_t)lds_max) --cap;
+    jp.stage_cap = cap >= 4 ? cap : 0;
+    if (const char* sc = knob("PINOT_AMD_STAGE_CAP")) jp.stage_cap = std::min(jp.stage_cap, atoi(sc));
+    jp.flush_every = (int)std::min<int64_t>(64, std::max<int64_t>(1, env_i64("PINOT_AMD_FLUSH_EVERY", 1)));
+    jp.flush_group = env_is("PINOT_AMD_FLUSH_GROUP", "1");
+  }
+  {  // algorithmic bytes: each decoded column once (fixed-bit at its width, raw at its value width)
+    for (size_t k = 0; k < L.segs.size(); ++k)
+      for (int sl = 0; sl < nslots; ++sl) {
+        L.col_bytes += stream_bpr(ls[k].cols[sl], L.packed >> sl & 1u) * (double)ls[k].num_docs;
+      }
+    std::vector<int> gate(nclauses, 1), has(nclauses, 0);
+    for (const JitLeaf& jl : jp.leaves) {
+      has[jl.clause] = 1;
+      if (jl.kinds != (1u << LEAF_DOC_BITSET) || jl.negate) gate[jl.clause] = 0;
+    }
+    for (int c = 0; c < nclauses; ++c) L.gated |= gate[c] && has[c];
+    if (jp.filter_gate) {  // filter columns of every doc, the key / value columns of the matching docs
+      L.fgate = true;
+      for (size_t k = 0; k < L.segs.size(); ++k)
+        for (int sl = 0; sl < nslots; ++sl) {
+          const double bpr = stream_bpr(ls[k].cols[sl], L.packed >> sl & 1u);  // both parts stream the twins
+          if (leaf_slot[sl]) L.filter_bytes += bpr * (double)ls[k].num_docs;
+          if (value_slot[sl] && k == 0) L.value_bpr += bpr;
+        }
+    }
+    // gated plans: column loads D tiles ahead of their gate, gate words 2D ahead. Measured on the
+    // inverted-index sweep, deeper pipelines only add registers (the gated loop is bound by its
+    // per-tile overhead, not by load latency), so the row-width depth stays.
+  }
+  return 0;
+}
+
+// helper kernels derived from the launch's shape: the admission's first-doc / sequential passes and the
+// segment-level trim's presence pass, with their grids
+int PlanBuild::launch_helper_passes(LaunchBuild& lb) {
+  Launch& L = lb.L;
+  std::vector<DevSegment>& ls = lb.ls;
+  JitPlan& jp = lb.jp;
+  const int64_t tiles = lb.tiles;
+  if (r->admit) {
+    // the admission's first-doc pass: the launch's filter + group key over each segment's prefix
+    JitPlan jf = jp;
+    jf.firstdoc = true;
+    jf.admit = jf.lds = jf.partitioned = jf.select = jf.word_select = jf.atomic_gate = jf.sample = false;
+    jf.part_sampled = false;
+    jf.aggregate = false;
+    jf.scan_nsub = 1;
+    jf.vals.clear();
+    jf.val_bits.clear();
+    jf.val_off.clear();
+    jf.rec_bytes = jf.stage_cap = jf.nparts = jf.key_shift = 0;
+    for (auto& lf : jf.leaves) lf.lds_words = lf.lut = 0;
+    L.jit_fd = jit_get(jf, &r->jit_status);
+    if (!L.jit_fd) return fail(PINOT_AMD_EUNSUPPORTED, "first-doc kernel unavailable: %s", r->jit_status.c_str());
+    if (r->q.num_keys <= kAdmitSeqMaxKeys && !env_is("PINOT_AMD_ADMIT_SEQ", "0")) {
+      JitPlan js = jf;
+      js.firstdoc = false;
+      js.admitseq = true;
+      std::string err;
+      L.jit_as = jit_get(js, &err);  // absent: the first-doc admission below serves
+    }
+    std::vector<DevSegment> fs;
+    int64_t ftiles = 0;
+    for (size_t k = 0; k < L.segs.size(); ++k) {
+      DevSegment d = ls[k];
+      d.num_docs = r->a_prefix[L.segs[k]];
+      // the prefix is the whole segment, or the segment cannot reach the limit (no pass: all admitted)
+      d.pad = (d.num_docs == 0 || d.num_docs >= ls[k].num_docs) ? 1 : 0;
+      d.tile_begin = ftiles;
+      ftiles += (d.num_docs + kTileDocs - 1) / kTileDocs;
+      fs.push_back(d);
+    }
+    if (int rc = L.d_fd_segs.alloc_copy(fs.data(), fs.size() * sizeof(DevSegment), 0)) return rc;
+    L.fd_q = L.q;
+    L.fd_q.total_tiles = ftiles;
+    int nf = occupancy_blocks(L.jit_fd->fn, kBlock, 0);
+    L.fd_grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * nf, ftiles));
+    L.fd_full_grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * nf, tiles));
+  }
+  if (r->seg_trim) {
+    // the segment-level safe trim's presence pass: the launch's filter (+ numGroupsLimit admission) and group
+    // key, each matching doc's ORDER BY rank marked in its segment's bitmap
+    JitPlan js = jp;
+    js.segpres = true;
+    js.lds = js.partitioned = js.select = js.word_select = js.atomic_gate = js.sample = js.part_sampled = false;
+    js.aggregate = false;
+    js.scan_nsub = 1;
+    js.sel_group = 1;
+    js.vals.clear();
+    js.val_bits.clear();
+    js.val_off.clear();
+    js.rec_bytes = js.stage_cap = js.nparts = js.key_shift = 0;
+    for (auto& lf : js.leaves) lf.lds_words = lf.lut = 0;
+    L.jit_sp = jit_get(js, &r->jit_status);
+    if (!L.jit_sp) return fail(PINOT_AMD_EUNSUPPORTED, "presence kernel unavailable: %s", r->jit_status.c_str());
+    int ns = occupancy_blocks(L.jit_sp->fn, kBlock, 0);
+    L.sp_grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * ns, tiles));
+  }
+  return 0;
+}
+
+// a partitioned launch: its companion scans, LDS sizes, grids and work-buffer needs; returns the scatter blocks
+// per CU
+int PlanBuild::launch_partitioned(LaunchBuild& lb) {
+  Launch& L = lb.L;
+  JitPlan& jp = lb.jp;
+  const int64_t tiles = lb.tiles;
+  const size_t li = lb.li;
+  JitPlan ja = jp;  // companion direct-atomic scan for batches where the filter keeps few docs
+  ja.partitioned = false;
+  ja.lds = false;
+  ja.scan_nsub = 1;
+  ja.atomic_gate = true;
+  ja.vals.clear();
+  ja.val_off.clear();
+  ja.rec_bytes = ja.stage_cap = ja.nparts = ja.key_shift = 0;
+  for (auto& a : ja.accs) a.narrow = 0;  // HBM table: full 128-bit adds
+  if (!env_is("PINOT_AMD_ATOMIC_HANDOVER", "0")) {
+    std::string err;
+    L.jit_atomic = jit_get(ja, &err);
+  }
+  L.part.atomic_threshold = L.jit_atomic ? L.docs / 64 : -1;
+  if (env_is("PINOT_AMD_ATOMIC_HANDOVER", "force") && L.jit_atomic) L.part.atomic_threshold = INT64_MAX;
+  // selectivity sample over every 32nd tile: when the extrapolated matches fall under the threshold
+  // the count pass steps aside and the direct-atomic scan is the only full pass
+  const int64_t stride = env_i64("PINOT_AMD_SAMPLE_STRIDE", 32);
+  if (!jp.part_sampled && L.jit_atomic && stride > 0 && tiles >= 64 * stride) {
+    JitPlan js = ja;
+    js.atomic_gate = false;
+    js.sample = true;
+    js.aggregate = false;
+    std::string err;
+    L.jit_sample = jit_get(js, &err);
+    if (L.jit_sample) L.part.sample_stride = stride;
+  }
+  L.part.nparts = jp.nparts;
+  L.part.key_shift = jp.key_shift;
+  for (size_t j = 0; j < part_vbase.size() && j < (size_t)kMaxAcc; ++j) L.part.vbase[j] = part_vbase[j];
+  L.shmem_scatter = jit_scatter_lds(jp, jp.stage_cap);
+  L.shmem_agg = (size_t)lds_arrays() * ((size_t)1 << jp.key_shift) * 8;
+  L.shmem = (size_t)jp.nparts * 4;
+  L.rec_bytes = jp.rec_bytes;
+  L.part_sampled = jp.part_sampled;
+  // sampled plans: the allotments may take 1.5 x docs + 256 records per partition (scaled to fit),
+  // the overflow slab every doc (it can never fill up)
+  L.region_cap = L.docs + L.docs / 2 + 256 * (int64_t)jp.nparts;
+  max_rec = std::max(max_rec, (size_t)(jp.part_sampled ? L.region_cap : L.docs) * jp.rec_bytes + 256);
+  if (jp.part_sampled) {
+    max_slab = std::max(max_slab, (size_t)L.docs * jp.rec_bytes + 256);
+    max_slab_docs = std::max(max_slab_docs, (size_t)L.docs + 64);
+  }
+  const int per_cu = occupancy_blocks(L.jit->fn_scatter, kBlock * kPartSub, L.shmem_scatter);
+  int na = occupancy_blocks(L.jit->fn_agg, 1024, L.shmem_agg);
+  L.agg_grid = cus * na;
+  if (L.jit_atomic) {
+    int nt = occupancy_blocks(L.jit_atomic->fn, kBlock, 0);
+    L.atomic_grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * nt, tiles));
+  }
+  if (L.jit_sample) {
+    int ns = occupancy_blocks(L.jit_sample->fn, kBlock, 0);
+    const int64_t vt = (tiles + L.part.sample_stride - 1) / L.part.sample_stride;
+    L.sample_grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * ns, (vt + 3) / 4));
+  }
+  L.part.counts = (unsigned long long*)r->matched.p + 3 * li;
+  L.part.check = (unsigned long long*)r->matched.p + 3 * nl + 2;
+  return per_cu;
+}
+
+// a selection-vector launch: select and gather grids, the vector chunk a wave reserves, the vector's size;
+// returns the select blocks per CU
+int PlanBuild::launch_select(LaunchBuild& lb) {
+  Launch& L = lb.L;
+  std::vector<DevSegment>& ls = lb.ls;
+  JitPlan& jp = lb.jp;
+  // select pass: plain 256-thread blocks without LDS; gather pass: the table's block size and LDS
+  L.select = true;
+  L.word_select = jp.word_select;
+  L.scan_nsub = 1;
+  L.gather_threads = jp.lds ? kBlock * jp.scan_nsub : kBlock;
+  int nb = occupancy_blocks(L.jit->fn, kBlock, 0);
+  const int ng = occupancy_blocks(L.jit->fn_gather, L.gather_threads, L.shmem);
+  // select blocks per CU: fewer, longer-running waves reserve vector chunks on the shared counter
+  // fewer times (same-address atomics serialise at the memory side). The word-level select reads
+  // little per doc and is bound by those reservations: 4 per CU (swept 1/2/4/8: 1 % inverted
+  // 1.42/1.31/1.27/1.38 ms); the tile-level select needs its occupancy (2 per CU: SSB Q1.2 0.65 -> 0.92 ms)
+  if (jp.word_select) nb = std::min(nb, 4);
+  L.gather_grid = cus * ng;
+  for (size_t k = 0; k < L.segs.size(); ++k)
+    for (int sl = 0; sl < nslots; ++sl) {
+      // the select pass streams the filter columns (their twins where used); the gather reads raw bytes
+      if (leaf_slot[sl]) L.filter_bytes += stream_bpr(ls[k].cols[sl], L.packed >> sl & 1u) * (double)ls[k].num_docs;
+      if (value_slot[sl] && k == 0) L.value_bpr += slot_bpr(ls[k].cols[sl]);
+    }
+  // Vector chunk a wave reserves at a time (plan-time counts): a power of two in [256, 4096] for the
+  // tile-level select, [64, 4096] for the word-level one; runs split across chunks in both.
+  int64_t m = 0, mt = 0;
+  for (int si : L.segs) {  // + padding: one run per 256-doc wave tile, or per lane's 256 docs
+    mt += seg_matched[si];
+    m += seg_matched[si] + 3 * std::min<int64_t>(seg_matched[si], (segs[si]->num_docs + 255) / 256 + 1);
+  }
+  const int64_t waves = (int64_t)cus * nb * 4;
+  // (runs continue over chunk ends, so a chunk is filled: the only padding is each wave's last chunk's
+  // tail, written by the select and read by the gather -- a quarter of the matches a wave expects
+  // keeps it small without many reservations)
+  // (word level: about twice the matches a wave expects, its reservations measured as its bound)
+  int64_t chunk = jp.word_select ? 64 : 256;
+  const int64_t want = jp.word_select ? 2 * mt / std::max<int64_t>(waves, 1) : mt / std::max<int64_t>(4 * waves, 1);
+  while (chunk < 4096 && chunk < want) chunk *= 2;
+  L.q.sel_chunk = (int32_t)chunk;
+  const int64_t per_chunk = chunk;
+  const int64_t chunks = (m + per_chunk - 1) / per_chunk + waves + 1;
+  max_sel = std::max<int64_t>(max_sel, chunks * chunk + 64);
+  return nb;
+}
+
+// one launch: descriptors, kernel shape, kernels, LDS sizes and grid
+int PlanBuild::plan_launch(size_t li) {
+  LaunchBuild lb{li, r->launches[li]};
+  Launch& L = lb.L;
+  if (int rc = launch_segments(lb)) return rc;
+  if (int rc = launch_shape(lb)) return rc;
+  const JitPlan& jp = lb.jp;
+  const int64_t tiles = lb.tiles;
+  L.jit = jit_get(jp, &r->jit_status);
+  if (!L.jit) return fail(PINOT_AMD_EUNSUPPORTED, "scan kernel unavailable: %s", r->jit_status.c_str());
+  if (jp.hash && jp.hash_spill && jp.hash_lds > 0 && !env_is("PINOT_AMD_HASH_DIRECT", "0")) {
+    // the same scan without the LDS level, for keys without skew (a 64-slot table stays for the shared code)
+    JitPlan jd = jp;
+    jd.hash_direct = true;
+    jd.hash_lds = 64;
+    jd.hash_admit = 0;
+    std::string err;
+    L.jit_direct = jit_get(jd, &err);  // absent: the LDS-level plan serves every execution
+    L.shmem_direct = (size_t)(hash_lds_bytes / jp.hash_lds) * 64;
+    if (L.jit_direct && env_is("PINOT_AMD_HASH_DIRECT", "force")) r->hash_mode = 1;  // (tests: from the first execution)
+    r->direct_place = env_is("PINOT_AMD_HASH_DIRECT", "force") || env_is("PINOT_AMD_HASH_DIRECT", "place");
+  }
+  if (int rc = launch_helper_passes(lb)) return rc;
+  L.scan_nsub = jp.partitioned ? 1 : jp.scan_nsub;
+  L.shmem = jp.lds && !jp.partitioned ? (size_t)lds_bytes : jp.hash_lds ? (size_t)hash_lds_bytes : 0;
+  for (const JitLeaf& jl : jp.leaves) L.shmem_sets += (size_t)jl.lds_words * 4;
+  {  // LDS accept tables: one per (clause, column) mask group with a lookup table (jit.cpp's layout)
+    std::vector<std::pair<int, int>> groups;
+    for (const JitLeaf& jl : jp.leaves) {
+      if (!jl.mask || !jl.lut) continue;
+      const std::pair<int, int> g{jl.clause, jl.slot};
+      if (std::find(groups.begin(), groups.end(), g) != groups.end()) continue;
+      groups.push_back(g);
+      L.shmem_sets += (size_t)(((1 << jl.lut) + 3) / 4) * 4;
+    }
+  }
+  if (!jp.select) L.shmem += L.shmem_sets;  // a select pass has no table: its sets start at 0
+  if (L.jit_direct) L.shmem_direct += L.shmem_sets;
+  const int per_cu = jp.partitioned ? launch_partitioned(lb)
+                     : jp.select    ? launch_select(lb)
+                                    : occupancy_blocks(L.jit->fn, kBlock * L.scan_nsub, L.shmem);
+  // persistent grid: resident blocks per CU x CUs (a larger grid would only queue a tail)
+  int64_t grid = (int64_t)cus * per_cu;
+  if (grid > tiles) grid = std::max<int64_t>(tiles, 1);
+  {
+    const int sub = jp.partitioned ? kPartSub : L.scan_nsub;  // tiles a block takes per step
+    if (sub > 1 && grid * sub > tiles) grid = std::max<int64_t>((tiles + sub - 1) / sub, 1);
+  }
+  if (L.part_sampled) {  // allotment tables of <= 2 x CUs scatter blocks sit behind the aggregation table
+    grid = std::min<int64_t>(grid, 2 * (int64_t)cus);
+    L.shmem_agg += (size_t)(2 * grid + 1) * 8;
+  }
+  L.grid = (int)grid;
+  if (jp.partitioned) max_count_cells = std::max(max_count_cells, (size_t)jp.nparts * (size_t)grid * kPartCountRatio);
+  return 0;
+}
+
+int PlanBuild::plan_launches() {
+  DevQuery& q = r->q;
   // Whole-query-narrow integer sums (JitAcc::hbm_narrow): when a SUM's value range times all the query's
   // docs fits int64, its adds into the HBM table need no carry, so they are one non-returning 64-bit atomic
   // on the low word (the 128-bit add waits for the old value to carry into the high word) and the plan's
@@ -4205,27 +4677,12 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
   // tables merge into the final table before the plan's end.
   {
     std::vector<int32_t> arrs;
-    if (!r->trim && q.nacc > 0 && !env_is("PINOT_AMD_HBM_NARROW", "0")) {
-      auto maxabs = [&](int sl) -> __int128 {
-        __int128 m = 0;
-        for (auto* s : segs) {
-          const Column& c = *s->cols.at(slot_cols[sl]);
-          if (!c.has_range) return -1;
-          const __int128 a = c.vmax < 0 ? -(__int128)c.vmax : (__int128)c.vmax;
-          const __int128 b = c.vmin < 0 ? -(__int128)c.vmin : (__int128)c.vmin;
-          m = std::max(m, std::max(a, b));
-        }
-        return m;
-      };
+    if (!r->trim && q.nacc > 0) {
       for (size_t ai = 0; ai < base.accs.size(); ++ai) {
         JitAcc& a = base.accs[ai];
         a.hbm_narrow = 0;
         if (a.op != ACC_SUM_I128) continue;
-        __int128 m = maxabs(a.slot);
-        if (m >= 0 && a.expr != EXPR_COL) {
-          const __int128 m2 = maxabs(a.slot2);
-          m = m2 < 0 ? -1 : a.expr == EXPR_MUL ? m * m2 : m + m2;
-        }
+        const __int128 m = acc_maxabs(segs, slot_cols, a);
         if (m >= 0 && m * (__int128)std::max<int64_t>(all_docs, 1) <= (__int128)INT64_MAX) {
           a.hbm_narrow = 1;
           arrs.push_back((int32_t)ai + 1);  // HBM array of its low word (array 0 is COUNT)
@@ -4237,476 +4694,17 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
     if (!arrs.empty())
       if (int rc = r->d_sext.alloc_copy(arrs.data(), arrs.size() * 4, 0)) return rc;
   }
-  const size_t nl = r->launches.size();
+  nl = r->launches.size();
   if (int rc = r->matched.alloc((3 * nl + 3) * sizeof(unsigned long long))) return rc;
   HIP_OK(hipMemset(r->matched.p, 0, r->matched.n));
-  size_t max_count_cells = 0, max_rec = 0, max_slab = 0, max_slab_docs = 0;
-  int64_t max_sel = 0;  // selection-vector entries of the largest select launch
-  for (size_t li = 0; li < nl; ++li) {
-    Launch& L = r->launches[li];
-    std::vector<DevSegment> ls;
-    std::vector<uint64_t*> lbits;
-    int64_t tiles = 0;
-    for (int si : L.segs) {
-      DevSegment ds = hsegs[si];
-      ds.tile_begin = tiles;
-      ds.key_seg = r->admit ? si : key_seg[si];
-      ds.pad = r->admit ? 1 : 0;  // sequential admission over whole segments: each one walked to its end
-      // (a tile-level select with G tiles per step: the segment's range padded to a multiple of G; the
-      // padding tiles match nothing and read only their columns' staging padding)
-      const int64_t G = base.sel_group;
-      tiles += ((segs[si]->num_docs + kTileDocs - 1) / kTileDocs + G - 1) / G * G;
-      L.docs += segs[si]->num_docs;
-      ls.push_back(ds);
-      lbits.push_back(bitset_ptrs[si]);
-    }
-    L.tiles = tiles;
-    L.q = q;
-    L.q.nsegs = (int32_t)L.segs.size();
-    L.q.total_tiles = tiles;
-    if (int rc = L.d_segs.alloc_copy(ls.data(), ls.size() * sizeof(DevSegment), 0)) return rc;
-    static_assert(sizeof(DevSegment) % 8 == 0, "the count pass checksums descriptors in 8-byte words");
-    L.h_segs = ls;
-    // fused when few docs match (measured: 0.01 % / 0.1 % of 1B rows 0.36 / 0.52 -> 0.24 / 0.42 ms; at
-    // 1 % the separate expansion's occupancy wins, 1.08 vs 1.17 ms); PINOT_AMD_FUSED_INV_SELECT=1 forces it
-    double lm = 0, ld = 0;
-    for (int si : L.segs) {
-      lm += seg_matched.empty() ? 0.0 : (double)seg_matched[si];
-      ld += (double)segs[si]->num_docs;
-    }
-    const bool fuse = env_is("PINOT_AMD_FUSED_INV_SELECT", "1") ||
-                      (!env_is("PINOT_AMD_FUSED_INV_SELECT", "0") && !seg_matched.empty() && lm <= 0.004 * ld);
-    if (base.word_select && fuse) {
-      // the launch's segments as work items of G-chunk groups; each inverted-index leaf mapped to its
-      // expansion job (its DevLeaf::bits is the job's bitset buffer)
-      const int G = expand_group();
-      std::vector<FusedSelSeg> fv(ls.size());
-      int64_t items = 0;
-      bool ok = true, neg_bits = false;
-      for (size_t k = 0; k < ls.size(); ++k) {
-        FusedSelSeg& f = fv[k];
-        memset(&f, 0, sizeof(f));
-        f.item_begin = items;
-        f.seg = (int32_t)k;
-        const int64_t words = (segs[L.segs[k]]->num_docs + kTileDocs - 1) / kTileDocs * (kTileDocs / 64);
-        f.nitems = (int32_t)((words + 1024 * G - 1) / (1024 * G));
-        for (int j = 0; j < kMaxLeaves; ++j) f.job[j] = -1;
-        for (size_t j = 0; j < order.size(); ++j) {
-          if (ls[k].leaves[j].kind != LEAF_DOC_BITSET) continue;
-          for (size_t ii = 0; ii < r->inv_leaves.size(); ++ii)
-            if (r->inv_leaves[ii].bitset->p == (const void*)ls[k].leaves[j].bits) f.job[j] = (int32_t)ii;
-          ok &= f.job[j] >= 0 && r->inv_leaves[f.job[j]].nchunks >= f.nitems;
-          neg_bits |= ls[k].leaves[j].negate != 0;
-        }
-        items += f.nitems;
-      }
-      if (ok) {
-        if (int rc = L.d_fused.alloc_copy(fv.data(), fv.size() * sizeof(FusedSelSeg), 0)) return rc;
-        L.fused = true;
-        L.nfused = (int32_t)fv.size();
-        L.fused_items = items;
-        L.fused_leaves = (int32_t)order.size();
-        // the clause-fold variant measured 5-9 % faster (sweep_inv_fused_variant.txt); negated bitset leaves need
-        // the per-leaf fold
-        L.fused_clause = !neg_bits && !env_is("PINOT_AMD_FUSED_VARIANT", "leaf");
-        L.fused_clauses = base.nclauses;
-      }
-    }
-    if (filter_only)
-      if (int rc = L.d_bitset_ptrs.alloc_copy(lbits.data(), lbits.size() * sizeof(uint64_t*), 0)) return rc;
+  for (size_t li = 0; li < nl; ++li)
+    if (int rc = plan_launch(li)) return rc;
+  return 0;
+}
 
-    JitPlan jp = base;
-    for (int sl = 0; sl < nslots; ++sl) {
-      const int enc = ls[0].cols[sl].enc;
-      JitSlot js{enc, ls[0].cols[sl].type, 0, 0};
-      if (enc != ENC_RAW) {  // dictionary of <= 64 entries everywhere: lane-register table
-        bool small = true;
-        for (auto& d : ls) small &= d.cols[sl].card <= 64 && d.cols[sl].card > 0;
-        js.dict_regs = small ? 1 : 0;
-      }
-      if (enc == ENC_FIXED_BIT) {  // width shared by the launch (<= 15): compile-time shifts
-        js.bits = ls[0].cols[sl].bits;
-        for (auto& d : ls)
-          if (d.cols[sl].bits != js.bits) js.bits = 0;
-        if (js.bits > 15 || generic_bits) js.bits = 0;
-      }
-      if (L.packed >> sl & 1u) {  // the twin's plane widths: the same in every segment of the launch
-        // (a select pass streams the filter columns only; its gather reads the other columns' raw bytes)
-        bool same = enc == ENC_RAW && !(jp.select && !leaf_slot[sl]);
-        for (auto& d : ls)
-          same &= d.cols[sl].for_twin && d.cols[sl].for_lo_bits == ls[0].cols[sl].for_lo_bits &&
-                  d.cols[sl].for_hi_bits == ls[0].cols[sl].for_hi_bits;
-        if (same) {
-          js.packed = 1;
-          js.for_lo = ls[0].cols[sl].for_lo_bits;
-          js.for_hi = ls[0].cols[sl].for_hi_bits;
-        } else {
-          L.packed &= ~(1u << sl);
-        }
-      }
-      jp.slots.push_back(js);
-    }
-    for (size_t k = 0; k < order.size(); ++k) {
-      JitLeaf jl{pred_slot[order[k]], Q.preds[order[k]].clause, ls[0].leaves[k].negate, 0u};
-      bool small_sets = jl.slot >= 0;
-      for (auto& d : ls) {
-        jl.kinds |= 1u << d.leaves[k].kind;
-        if (jl.slot >= 0) small_sets &= d.cols[jl.slot].card < 64 * 32;
-      }
-      jl.bits_regs = (small_sets && (jl.kinds & (1u << LEAF_DICT_SET))) ? 1 : 0;
-      // accept masks: a dictionary column of <= 64 values in every segment, leaves that are dictId ranges /
-      // sets / constants (one bit extract per doc instead of a range compare or a set lookup)
-      {
-        const uint32_t ok = (1u << LEAF_DICT_RANGE) | (1u << LEAF_DICT_SET) | (1u << LEAF_CONST);
-        int64_t maxc = 0;
-        bool dict = jl.slot >= 0 && ls[0].cols[jl.slot].enc != ENC_RAW;
-        for (auto& d : ls) if (jl.slot >= 0) maxc = std::max<int64_t>(maxc, d.cols[jl.slot].card);
-        if (dict && !(jl.kinds & ~ok) && (jl.kinds & ((1u << LEAF_DICT_RANGE) | (1u << LEAF_DICT_SET))) && maxc <= 64 &&
-            !env_is("PINOT_AMD_LEAF_MASKS", "0")) {
-          jl.mask = maxc <= 32 ? 1 : 2;
-          jl.bits_regs = 0;
-          // fixed-bit columns of <= 6 bits in 256-thread scan / select blocks: an LDS accept table per
-          // (clause, column) indexed by F = 4, 2 or 1 packed fields (4 / F lookups per lane of 4 docs), the
-          // table at most 2^PINOT_AMD_LUT_MAX_BITS bytes (default 12: 4 KiB, one lookup per 4 docs for <= 3
-          // bits). Tables of <= 2^8 bytes (one dword per LDS bank) never conflict, but the extra lookups
-          // cost more than the ~6 conflict cycles they save: SSB 8.50 -> 8.56 ms at a 2^8 cap
-          // (profiles/r04/sweep_ssb_lut_cap.txt) -- the select pass is latency-bound, not LDS-bound.
-          const JitSlot& js = jp.slots[jl.slot];
-          static const int lut_max = (int)std::min<int64_t>(12, std::max<int64_t>(6, env_i64("PINOT_AMD_LUT_MAX_BITS", 12)));
-          if (js.enc == ENC_FIXED_BIT && js.bits >= 1 && js.bits <= 6 && !jp.partitioned &&
-              (jp.scan_nsub == 1 || jp.select) && !env_is("PINOT_AMD_LEAF_LUT", "0"))
-            jl.lut = 4 * js.bits <= lut_max ? 4 * js.bits : 2 * js.bits <= lut_max ? 2 * js.bits : js.bits;
-        }
-      }
-      // larger dictId sets (<= 4096 words) are read from LDS, not from global memory per doc, by the
-      // 256-thread blocks of non-partitioned plans (fused scans with nsub 1, every select pass)
-      if (!jl.bits_regs && !jl.mask && jl.slot >= 0 && (jl.kinds & (1u << LEAF_DICT_SET)) && !jp.partitioned &&
-          (jp.scan_nsub == 1 || jp.select) && !env_is("PINOT_AMD_LDS_SETS", "0")) {
-        int64_t w = 0;
-        for (auto& d : ls) w = std::max<int64_t>(w, (d.cols[jl.slot].card >> 5) + 1);
-        int64_t used = 0;
-        for (auto& o : jp.leaves) used += o.lds_words;
-        w = (w + 3) & ~(int64_t)3;
-        if (w <= 4096 && used + w <= 8192) jl.lds_words = (int)w;
-      }
-      jp.leaves.push_back(jl);
-    }
-    {  // pipeline depth: ~4 KiB in flight per wave (256 docs x bytes per row)
-      double bpr = 0;
-      for (size_t sl = 0; sl < jp.slots.size(); ++sl) {
-        if (jp.select && !leaf_slot[sl]) continue;  // a select pass streams the filter columns only
-        const JitSlot& js = jp.slots[sl];
-        bpr += js.enc == ENC_FIXED_BIT ? (js.bits > 0 ? js.bits : 16) / 8.0
-               : js.packed            ? (js.for_lo + js.for_hi) / 8.0  // the bytes the launch streams
-               : js.enc == ENC_RAW    ? value_size(js.type) : 0.0;
-      }
-      jp.depth = bpr <= 0 ? 1 : (int)std::min(4.0, std::max(1.0, std::ceil(4096.0 / (256.0 * bpr))));
-      // a select step of G tiles loads G tiles per register set: the same bytes in flight with 1/G the sets
-      if (jp.sel_group > 1) jp.depth = std::max(1, (jp.depth + jp.sel_group - 1) / jp.sel_group);
-      if (const char* pd = knob("PINOT_AMD_PREFETCH")) jp.depth = std::max(1, std::min(8, atoi(pd)));
-      if (env_is("PINOT_AMD_LANE_TABLES", "0")) {
-        for (auto& js : jp.slots) js.dict_regs = 0;
-        for (auto& jl : jp.leaves) jl.bits_regs = 0;
-      }
-      if (const char* pw = knob("PINOT_AMD_WAVES_PER_EU")) jp.waves_per_eu = std::max(0, std::min(8, atoi(pw)));
-      // non-temporal column loads for wide-row fused scans (configs[1]: 3.58 -> 3.51 ms per 1B rows); the
-      // narrow SSB select passes measured 1-3 % slower with them, the partitioned scatter 10 % slower
-      // bpr counts the bytes the launch streams (packed twins at their plane widths): configs[1] with twins is
-      // 15.375 B/row and still gains from the hint (2.665 -> 2.588 ms per 1B rows, profiles/r07/sweep_packed.txt),
-      // so the bound sits at 15 B/row; rows between the SSB passes' widths and 15 B were not measured
-      jp.nt_loads = env_is("PINOT_AMD_NT_LOADS", "1") ||
-                    (!env_is("PINOT_AMD_NT_LOADS", "0") && bpr >= 15.0 && !jp.partitioned && !jp.select);
-      // XCD-aware tile ranges where blocks read per-segment tables beside the columns: the admission bitmaps
-      // (128 KiB per segment for configs[3]) thrashed each XCD's L2 when its blocks spanned every segment
-      // (default-limit configs[3] scatter: 20.1 -> 8.8 GB fetched per 400M rows, 4.87 -> 4.15 ms per plan;
-      // profiles/r05/pmc_hcdef_xcd.txt). PINOT_AMD_XCD_REMAP=0|1 pins it.
-      jp.xcd_remap = env_is("PINOT_AMD_XCD_REMAP", "1") || (jp.admit && !env_is("PINOT_AMD_XCD_REMAP", "0"));
-#ifdef PINOT_AMD_DIAGNOSTICS
-      // measurement-only variants that void the results (round-5 profiles): built with -DPINOT_AMD_DIAGNOSTICS only
-      jp.diag_admit_off = env_is("PINOT_AMD_DIAG_ADMIT_OFF", "1");
-      if (jp.partitioned) {
-        const int64_t w = env_i64("PINOT_AMD_DIAG_REC_WRAP", 0);
-        jp.diag_rec_wrap = (w >= 4096 && (w & (w - 1)) == 0) ? w : 0;
-      }
-#endif
-    }
-    if (jp.partitioned) {
-      jit_layout_records(&jp);
-      // sampled allotments replace the exact count pass once the strided histogram has >= 64 tiles
-      const int64_t stride = env_i64("PINOT_AMD_SAMPLE_STRIDE", 32);
-      jp.part_sampled = stride > 0 && tiles >= 64 * stride && !env_is("PINOT_AMD_PART_SAMPLED", "0");
-      if (jp.part_sampled) L.part.sample_stride = stride;
-      // scatter staging: as many records per partition as the LDS holds (up to 64); below 4 a run is
-      // too short to pay for the staging round trip and records are written directly
-      // PINOT_AMD_PART_SUB: 256-thread groups per scatter block (4: one CU-wide block per CU, 2 / 1: two / four
-      // blocks per CU sharing the LDS)
-      jp.part_sub = (int)env_i64("PINOT_AMD_PART_SUB", kPartSub);
-      if (jp.part_sub != 1 && jp.part_sub != 2) jp.part_sub = kPartSub;
-      const size_t stage_lds = (size_t)lds_max / (size_t)(kPartSub / jp.part_sub);
-      // admission plans: the segment's admission bitmap beside the staging (an LDS read per doc instead of a
-      // dependent global load; the scatter writes only the admitted docs' records, so a short staging serves)
-      jp.admit_lds = jp.admit && jp.part_sub == kPartSub && !env_is("PINOT_AMD_ADMIT_LDS", "0") &&
-                     jit_scatter_lds([&] { JitPlan t = jp; t.admit_lds = true; return t; }(), 4) <= stage_lds;
-      int cap = 64;
-      while (cap >= 4 && jit_scatter_lds(jp, cap) > stage_lds) --cap;
-      jp.stage_cap = cap >= 4 ? cap : 0;
-      if (const char* sc = knob("PINOT_AMD_STAGE_CAP")) jp.stage_cap = std::min(jp.stage_cap, atoi(sc));
-      jp.flush_pct = (int)std::min<int64_t>(100, std::max<int64_t>(1, env_i64("PINOT_AMD_FLUSH_PCT", 85)));
-      jp.flush_every = (int)std::min<int64_t>(64, std::max<int64_t>(1, env_i64("PINOT_AMD_FLUSH_EVERY", 1)));
-      jp.flush_par = !env_is("PINOT_AMD_FLUSH_PAR", "0");
-      jp.flush_group = env_is("PINOT_AMD_FLUSH_GROUP", "1");
-      jp.scatter_batch = !env_is("PINOT_AMD_SCATTER_BATCH", "0");
-    }
-    {  // algorithmic bytes: each decoded column once (fixed-bit at its width, raw at its value width)
-      for (size_t k = 0; k < L.segs.size(); ++k)
-        for (int sl = 0; sl < nslots; ++sl) {
-          L.col_bytes += stream_bpr(ls[k].cols[sl], L.packed >> sl & 1u) * (double)ls[k].num_docs;
-        }
-      std::vector<int> gate(nclauses, 1), has(nclauses, 0);
-      for (const JitLeaf& jl : jp.leaves) {
-        has[jl.clause] = 1;
-        if (jl.kinds != (1u << LEAF_DOC_BITSET) || jl.negate) gate[jl.clause] = 0;
-      }
-      for (int c = 0; c < nclauses; ++c) L.gated |= gate[c] && has[c];
-      if (jp.filter_gate) {  // filter columns of every doc, the key / value columns of the matching docs
-        L.fgate = true;
-        for (size_t k = 0; k < L.segs.size(); ++k)
-          for (int sl = 0; sl < nslots; ++sl) {
-            const double bpr = stream_bpr(ls[k].cols[sl], L.packed >> sl & 1u);  // both parts stream the twins
-            if (leaf_slot[sl]) L.filter_bytes += bpr * (double)ls[k].num_docs;
-            if (value_slot[sl] && k == 0) L.value_bpr += bpr;
-          }
-      }
-      // gated plans: column loads D tiles ahead of their gate, gate words 2D ahead. Measured on the
-      // inverted-index sweep, deeper pipelines only add registers (the gated loop is bound by its
-      // per-tile overhead, not by load latency), so the row-width depth stays unless overridden.
-      if (L.gated && knob("PINOT_AMD_GATE_DEPTH"))
-        jp.depth = (int)std::min<int64_t>(std::max<int64_t>(env_i64("PINOT_AMD_GATE_DEPTH", 1), 1), 4);
-    }
-    L.jit = jit_get(jp, &r->jit_status);
-    if (!L.jit) return fail(PINOT_AMD_EUNSUPPORTED, "scan kernel unavailable: %s", r->jit_status.c_str());
-    if (jp.hash && jp.hash_spill && jp.hash_lds > 0 && !env_is("PINOT_AMD_HASH_DIRECT", "0")) {
-      // the same scan without the LDS level, for keys without skew (a 64-slot table stays for the shared code)
-      JitPlan jd = jp;
-      jd.hash_direct = true;
-      jd.hash_lds = 64;
-      jd.hash_admit = 0;
-      std::string err;
-      L.jit_direct = jit_get(jd, &err);  // absent: the LDS-level plan serves every execution
-      L.shmem_direct = (size_t)(hash_lds_bytes / jp.hash_lds) * 64;
-      if (L.jit_direct && env_is("PINOT_AMD_HASH_DIRECT", "force")) r->hash_mode = 1;  // (tests: from the first execution)
-      r->direct_place = env_is("PINOT_AMD_HASH_DIRECT", "force") || env_is("PINOT_AMD_HASH_DIRECT", "place");
-    }
-    if (r->admit) {
-      // the admission's first-doc pass: the launch's filter + group key over each segment's prefix
-      JitPlan jf = jp;
-      jf.firstdoc = true;
-      jf.admit = jf.lds = jf.partitioned = jf.select = jf.word_select = jf.atomic_gate = jf.sample = false;
-      jf.part_sampled = false;
-      jf.aggregate = false;
-      jf.scan_nsub = 1;
-      jf.vals.clear();
-      jf.val_bits.clear();
-      jf.val_off.clear();
-      jf.rec_bytes = jf.stage_cap = jf.nparts = jf.key_shift = 0;
-      for (auto& lf : jf.leaves) lf.lds_words = lf.lut = 0;
-      L.jit_fd = jit_get(jf, &r->jit_status);
-      if (!L.jit_fd) return fail(PINOT_AMD_EUNSUPPORTED, "first-doc kernel unavailable: %s", r->jit_status.c_str());
-      if (r->q.num_keys <= kAdmitSeqMaxKeys && !env_is("PINOT_AMD_ADMIT_SEQ", "0")) {
-        JitPlan js = jf;
-        js.firstdoc = false;
-        js.admitseq = true;
-        std::string err;
-        L.jit_as = jit_get(js, &err);  // absent: the first-doc admission below serves
-      }
-      std::vector<DevSegment> fs;
-      int64_t ftiles = 0;
-      for (size_t k = 0; k < L.segs.size(); ++k) {
-        DevSegment d = ls[k];
-        d.num_docs = r->a_prefix[L.segs[k]];
-        // the prefix is the whole segment, or the segment cannot reach the limit (no pass: all admitted)
-        d.pad = (d.num_docs == 0 || d.num_docs >= ls[k].num_docs) ? 1 : 0;
-        d.tile_begin = ftiles;
-        ftiles += (d.num_docs + kTileDocs - 1) / kTileDocs;
-        fs.push_back(d);
-      }
-      if (int rc = L.d_fd_segs.alloc_copy(fs.data(), fs.size() * sizeof(DevSegment), 0)) return rc;
-      L.fd_q = L.q;
-      L.fd_q.total_tiles = ftiles;
-      int nf = 0;
-      if (occupancy_blocks(&nf, L.jit_fd->fn, kBlock, 0) != hipSuccess || nf < 1) nf = 1;
-      L.fd_grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * nf, ftiles));
-      L.fd_full_grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * nf, tiles));
-    }
-    if (r->seg_trim) {
-      // the segment-level safe trim's presence pass: the launch's filter (+ numGroupsLimit admission) and group
-      // key, each matching doc's ORDER BY rank marked in its segment's bitmap
-      JitPlan js = jp;
-      js.segpres = true;
-      js.lds = js.partitioned = js.select = js.word_select = js.atomic_gate = js.sample = js.part_sampled = false;
-      js.aggregate = false;
-      js.scan_nsub = 1;
-      js.sel_group = 1;
-      js.vals.clear();
-      js.val_bits.clear();
-      js.val_off.clear();
-      js.rec_bytes = js.stage_cap = js.nparts = js.key_shift = 0;
-      for (auto& lf : js.leaves) lf.lds_words = lf.lut = 0;
-      L.jit_sp = jit_get(js, &r->jit_status);
-      if (!L.jit_sp) return fail(PINOT_AMD_EUNSUPPORTED, "presence kernel unavailable: %s", r->jit_status.c_str());
-      int ns = 0;
-      if (occupancy_blocks(&ns, L.jit_sp->fn, kBlock, 0) != hipSuccess || ns < 1) ns = 1;
-      L.sp_grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * ns, tiles));
-    }
-    L.scan_nsub = jp.partitioned ? 1 : jp.scan_nsub;
-    L.shmem = jp.lds && !jp.partitioned ? (size_t)lds_bytes : jp.hash_lds ? (size_t)hash_lds_bytes : 0;
-    for (const JitLeaf& jl : jp.leaves) L.shmem_sets += (size_t)jl.lds_words * 4;
-    {  // LDS accept tables: one per (clause, column) mask group with a lookup table (jit.cpp's layout)
-      std::vector<std::pair<int, int>> groups;
-      for (const JitLeaf& jl : jp.leaves) {
-        if (!jl.mask || !jl.lut) continue;
-        const std::pair<int, int> g{jl.clause, jl.slot};
-        if (std::find(groups.begin(), groups.end(), g) != groups.end()) continue;
-        groups.push_back(g);
-        L.shmem_sets += (size_t)(((1 << jl.lut) + 3) / 4) * 4;
-      }
-    }
-    if (!jp.select) L.shmem += L.shmem_sets;  // a select pass has no table: its sets start at 0
-    if (L.jit_direct) L.shmem_direct += L.shmem_sets;
-    int per_cu = 1;
-    if (jp.partitioned) {
-      JitPlan ja = jp;  // companion direct-atomic scan for batches where the filter keeps few docs
-      ja.partitioned = false;
-      ja.lds = false;
-      ja.scan_nsub = 1;
-      ja.atomic_gate = true;
-      ja.vals.clear();
-      ja.val_off.clear();
-      ja.rec_bytes = ja.stage_cap = ja.nparts = ja.key_shift = 0;
-      for (auto& a : ja.accs) a.narrow = 0;  // HBM table: full 128-bit adds
-      if (!env_is("PINOT_AMD_ATOMIC_HANDOVER", "0")) {
-        std::string err;
-        L.jit_atomic = jit_get(ja, &err);
-      }
-      L.part.atomic_threshold = L.jit_atomic ? L.docs / 64 : -1;
-      if (env_is("PINOT_AMD_ATOMIC_HANDOVER", "force") && L.jit_atomic) L.part.atomic_threshold = INT64_MAX;
-      // selectivity sample over every 32nd tile: when the extrapolated matches fall under the threshold
-      // the count pass steps aside and the direct-atomic scan is the only full pass
-      const int64_t stride = env_i64("PINOT_AMD_SAMPLE_STRIDE", 32);
-      if (!jp.part_sampled && L.jit_atomic && stride > 0 && tiles >= 64 * stride) {
-        JitPlan js = ja;
-        js.atomic_gate = false;
-        js.sample = true;
-        js.aggregate = false;
-        std::string err;
-        L.jit_sample = jit_get(js, &err);
-        if (L.jit_sample) L.part.sample_stride = stride;
-      }
-      L.part.nparts = jp.nparts;
-      L.part.key_shift = jp.key_shift;
-      for (size_t j = 0; j < part_vbase.size() && j < (size_t)kMaxAcc; ++j) L.part.vbase[j] = part_vbase[j];
-      L.shmem_scatter = jit_scatter_lds(jp, jp.stage_cap);
-      L.shmem_agg = (size_t)lds_arrays() * ((size_t)1 << jp.key_shift) * 8;
-      L.shmem = (size_t)jp.nparts * 4;
-      L.rec_bytes = jp.rec_bytes;
-      L.part_sampled = jp.part_sampled;
-      // sampled plans: the allotments may take 1.5 x docs + 256 records per partition (scaled to fit),
-      // the overflow slab every doc (it can never fill up)
-      L.region_cap = L.docs + L.docs / 2 + 256 * (int64_t)jp.nparts;
-      max_rec = std::max(max_rec, (size_t)(jp.part_sampled ? L.region_cap : L.docs) * jp.rec_bytes + 256);
-      if (jp.part_sampled) {
-        max_slab = std::max(max_slab, (size_t)L.docs * jp.rec_bytes + 256);
-        max_slab_docs = std::max(max_slab_docs, (size_t)L.docs + 64);
-      }
-      int nb = 0;
-      L.part_sub = jp.part_sub;
-      if (occupancy_blocks(&nb, L.jit->fn_scatter, kBlock * jp.part_sub, L.shmem_scatter) !=
-              hipSuccess || nb < 1)
-        nb = 1;
-      per_cu = nb;
-      int na = 0;
-      if (occupancy_blocks(&na, L.jit->fn_agg, 1024, L.shmem_agg) != hipSuccess || na < 1)
-        na = 1;
-      L.agg_grid = cus * na;
-      if (L.jit_atomic) {
-        int nt = 0;
-        if (occupancy_blocks(&nt, L.jit_atomic->fn, kBlock, 0) != hipSuccess || nt < 1) nt = 1;
-        L.atomic_grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * nt, tiles));
-      }
-      if (L.jit_sample) {
-        int ns = 0;
-        if (occupancy_blocks(&ns, L.jit_sample->fn, kBlock, 0) != hipSuccess || ns < 1) ns = 1;
-        const int64_t vt = (tiles + L.part.sample_stride - 1) / L.part.sample_stride;
-        L.sample_grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * ns, (vt + 3) / 4));
-      }
-      L.part.counts = (unsigned long long*)r->matched.p + 3 * li;
-      L.part.check = (unsigned long long*)r->matched.p + 3 * nl + 2;
-    } else if (jp.select) {
-      // select pass: plain 256-thread blocks without LDS; gather pass: the table's block size and LDS
-      L.select = true;
-      L.word_select = jp.word_select;
-      L.scan_nsub = 1;
-      L.gather_threads = jp.lds ? kBlock * jp.scan_nsub : kBlock;
-      int nb = 0, ng = 0;
-      if (occupancy_blocks(&nb, L.jit->fn, kBlock, 0) != hipSuccess || nb < 1) nb = 1;
-      if (occupancy_blocks(&ng, L.jit->fn_gather, L.gather_threads, L.shmem) != hipSuccess ||
-          ng < 1)
-        ng = 1;
-      // select blocks per CU: fewer, longer-running waves reserve vector chunks on the shared counter
-      // fewer times (same-address atomics serialise at the memory side). The word-level select reads
-      // little per doc and is bound by those reservations: 4 per CU (swept 1/2/4/8: 1 % inverted
-      // 1.42/1.31/1.27/1.38 ms); the tile-level select needs its occupancy (2 per CU: SSB Q1.2 0.65 -> 0.92 ms)
-      if (jp.word_select) nb = std::min(nb, 4);
-      if (const char* e = knob("PINOT_AMD_SELECT_PER_CU")) nb = std::max(1, std::min(nb, atoi(e)));
-      per_cu = nb;
-      L.gather_grid = cus * ng;
-      if (const char* e = knob("PINOT_AMD_GATHER_BLOCKS")) L.gather_grid = std::max(1, std::min(L.gather_grid, atoi(e)));
-      for (size_t k = 0; k < L.segs.size(); ++k)
-        for (int sl = 0; sl < nslots; ++sl) {
-          // the select pass streams the filter columns (their twins where used); the gather reads raw bytes
-          if (leaf_slot[sl]) L.filter_bytes += stream_bpr(ls[k].cols[sl], L.packed >> sl & 1u) * (double)ls[k].num_docs;
-          if (value_slot[sl] && k == 0) L.value_bpr += slot_bpr(ls[k].cols[sl]);
-        }
-      // Vector chunk a wave reserves at a time (plan-time counts): a power of two in [256, 4096] for the
-      // tile-level select, [64, 4096] for the word-level one; runs split across chunks in both.
-      int64_t m = 0, mt = 0;
-      for (int si : L.segs) {  // + padding: one run per 256-doc wave tile, or per lane's 256 docs
-        mt += seg_matched[si];
-        m += seg_matched[si] + 3 * std::min<int64_t>(seg_matched[si], (segs[si]->num_docs + 255) / 256 + 1);
-      }
-      const int64_t waves = (int64_t)cus * nb * 4;
-      // (runs continue over chunk ends, so a chunk is filled: the only padding is each wave's last chunk's
-      // tail, written by the select and read by the gather -- a quarter of the matches a wave expects
-      // keeps it small without many reservations)
-      // (word level: about twice the matches a wave expects, its reservations measured as its bound)
-      int64_t chunk = jp.word_select ? 64 : 256;
-      const int64_t want = jp.word_select ? 2 * mt / std::max<int64_t>(waves, 1) : mt / std::max<int64_t>(4 * waves, 1);
-      while (chunk < 4096 && chunk < want) chunk *= 2;
-      L.q.sel_chunk = (int32_t)chunk;
-      const int64_t per_chunk = chunk;
-      const int64_t chunks = (m + per_chunk - 1) / per_chunk + waves + 1;
-      max_sel = std::max<int64_t>(max_sel, chunks * chunk + 64);
-    } else {
-      int nb = 0;
-      if (occupancy_blocks(&nb, L.jit->fn, kBlock * L.scan_nsub, L.shmem) != hipSuccess ||
-          nb < 1)
-        nb = 1;
-      per_cu = nb;
-    }
-    // persistent grid: resident blocks per CU x CUs (a larger grid would only queue a tail)
-    int64_t grid = (int64_t)cus * per_cu;
-    if (grid > tiles) grid = std::max<int64_t>(tiles, 1);
-    {
-      const int sub = jp.partitioned ? jp.part_sub : L.scan_nsub;  // tiles a block takes per step
-      if (sub > 1 && grid * sub > tiles) grid = std::max<int64_t>((tiles + sub - 1) / sub, 1);
-    }
-    if (L.part_sampled) {  // allotment tables of <= 2 x CUs scatter blocks sit behind the aggregation table
-      grid = std::min<int64_t>(grid, 2 * (int64_t)cus);
-      L.shmem_agg += (size_t)(2 * grid + 1) * 8;
-    }
-    L.grid = (int)grid;
-    if (jp.partitioned) max_count_cells = std::max(max_count_cells, (size_t)jp.nparts * (size_t)grid * kPartCountRatio);
-  }
+// the plan's device buffers, in a fixed order (the block pool's reuse depends on it)
+int PlanBuild::alloc_buffers() {
+  DevQuery& q = r->q;
   // partitioned work buffers, shared by the launches (they run one after another)
   if (r->kind == PLAN_PARTITIONED) {
     int maxp = 0;
@@ -4880,6 +4878,63 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
       L.q.seg_words = r->sp_words;
     }
   }
+  return 0;
+}
+
+}  // namespace
+
+static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, int32_t n, void* stream,
+                        bool filter_only, pinot_amd_result** out) {
+  if (!qq || !segs_in || n < 1 || !out) return fail(PINOT_AMD_EINVAL, "execute: bad arguments");
+  std::vector<pinot_amd_segment*> segs(segs_in, segs_in + n);
+  for (auto* s : segs)
+    if (!s) return fail(PINOT_AMD_EINVAL, "execute: null segment");
+  const std::string plan_key = plan_identity(*qq, segs, filter_only);
+  if (pinot_amd_result* hit = plan_cache_take(plan_key)) {  // a prepared plan of this identity: run it
+    std::unique_ptr<pinot_amd_result> hold(hit);
+    hit->stream = (hipStream_t)stream;
+    PlanClock clk(&hit->plan_timing);
+    clk.mark("plan_cache");
+    if (int rc = run_plan(hit)) return rc;
+    clk.mark("launch");
+    *out = hold.release();
+    return 0;
+  }
+  const size_t alloc0 = g_tl_alloc_bytes;
+  auto res = std::make_unique<pinot_amd_result>();
+  pinot_amd_result* r = res.get();
+  r->stream = (hipStream_t)stream;
+  r->plan_key = plan_key;
+  for (auto* sg : segs) r->plan_uids.push_back(sg->uid);
+  PlanClock clk(&r->plan_timing);
+  PlanBuild b;
+  b.qq = qq;
+  b.segs = std::move(segs);
+  b.n = n;
+  b.stream = stream;
+  b.filter_only = filter_only;
+  b.r = r;
+  if (int rc = b.raw_keys()) return rc;
+  clk.mark("raw_keys");
+  if (int rc = b.leaves()) return rc;
+  clk.mark("leaves");
+  if (int rc = b.keys_probe()) return rc;
+  clk.mark("keys_probe");
+  if (int rc = b.accs()) return rc;
+  clk.mark("accs");
+  if (int rc = b.plan_kind()) return rc;
+  clk.mark("plan_kind");
+  if (int rc = b.hash_sizes()) return rc;
+  clk.mark("hash_sizes");
+  if (int rc = b.dev_segs()) return rc;
+  clk.mark("dev_segs");
+  if (int rc = b.kernel_choices()) return rc;
+  clk.mark("kernel_choices");
+  if (int rc = b.select_plan()) return rc;
+  clk.mark("select_plan");
+  if (int rc = b.group_launches()) return rc;
+  if (int rc = b.plan_launches()) return rc;
+  if (int rc = b.alloc_buffers()) return rc;
   clk.mark("jit_alloc");
   HIP_OK(hipEventCreate(&r->ev0));
   HIP_OK(hipEventCreate(&r->ev1));
@@ -5217,7 +5272,7 @@ static std::string selfcheck_report(pinot_amd_result* r) {
       DevQuery q = L.q;
       void* args[] = {(void*)&segs, (void*)&q, (void*)&table, (void*)&bits, (void*)&matched, (void*)&pc, (void*)&h};
       std::vector<uint32_t> again(hist.size());
-      if (hipModuleLaunchKernel(L.jit->fn, (unsigned)cg, 1, 1, (unsigned)(kBlock * L.part_sub), 1, 1, (unsigned)L.shmem,
+      if (hipModuleLaunchKernel(L.jit->fn, (unsigned)cg, 1, 1, (unsigned)(kBlock * kPartSub), 1, 1, (unsigned)L.shmem,
                                 nullptr, args, nullptr) != hipSuccess ||
           hipMemcpy(again.data(), h2.p, again.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
         continue;

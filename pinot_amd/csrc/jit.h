@@ -10,7 +10,11 @@
 
 namespace pamd {
 
-constexpr int kPartSub = 4;  // partition count / scatter blocks: 4 x 256 threads (one block per CU)
+// partition count / scatter blocks: 4 x 256 threads (one CU-wide block per CU with all the LDS for staging;
+// two 512-thread blocks per CU, each with half the LDS, measured 11.28 -> 12.26 ms on configs[3],
+// profiles/r04/sweep_hc_part_sub.txt)
+constexpr int kPartSub = 4;
+constexpr int kFlushPct = 85;  // scatter: a partition is written out once this % of its staging is filled (swept: 85 best)
 constexpr int kPartCountRatio = 2;  // count-pass blocks per scatter-pass block (count needs little LDS)
 constexpr int64_t kAdmitSeqMaxKeys = 1 << 20;  // sequential admission: the seen-key bitmap (128 KiB) in LDS
 constexpr int kAdmitSeqSlots = 2048;           // its per-tile hash table of new keys (key, first doc)
@@ -87,7 +91,6 @@ struct JitPlan {
   bool lds = false;
   int scan_nsub = 1;           // 256-thread groups per scan block (4 for a table above 40 KiB)
   int depth = 1;               // software-pipeline depth (tiles prefetched ahead), 1..4
-  int waves_per_eu = 0;        // > 0: occupancy target handed to the register allocator
   bool nt_loads = false;       // column loads with the non-temporal hint (streamed once, no cache reuse)
   bool bitset = false;
   bool aggregate = true;
@@ -108,19 +111,13 @@ struct JitPlan {
   std::vector<int> val_off;
   int rec_bytes = 0;           // record size: 64-bit words x 8
   int stage_cap = 0;           // scatter: records staged per partition in LDS (0: direct writes)
-  int flush_pct = 85;          // scatter: a partition is written out once this % of its staging is filled (swept: 85 best)
   int flush_every = 1;         // scatter: the staged partitions are checked (two block barriers) every n tile steps
   // scatter: the wave's ready partitions are written out lane-parallel (their runs concatenated, each lane
-  // one 16 / 8 B unit, owners found by a binary search over the lanes' prefix sums) instead of one run
-  // after another with the whole wave on each run
-  bool flush_par = true;
-  // 16-byte records: the flush copies four ready partitions per wave step, a 16-lane group each (consecutive
-  // lanes store consecutive records), instead of the lane-parallel flush's per-unit owner search
+  // one 16 / 8 B unit, owners found by a binary search over the lanes' prefix sums); a lane's staging-slot
+  // atomics are issued together. flush_group, 16-byte records: the flush copies four ready partitions per wave
+  // step, a 16-lane group each (consecutive lanes store consecutive records), instead of the lane-parallel
+  // flush's per-unit owner search
   bool flush_group = false;
-  // partitioned plans: 256-thread groups per count / scatter block (4: one CU-wide block per CU with all the
-  // LDS for staging; 2 / 1: two / four blocks per CU, each with that share of the LDS)
-  int part_sub = kPartSub;
-  bool scatter_batch = true;  // scatter: a lane's staging-slot atomics issued together (PINOT_AMD_SCATTER_BATCH=0: one by one)
   // Sampled capacities instead of the exact count pass: a histogram over every sample_stride-th tile
   // sizes each partition's region (DevPartition::cap); the scatter reserves space with one global
   // atomic per flushed run, records beyond a region's capacity go to the overflow slab, aggregated
@@ -163,7 +160,6 @@ struct JitPlan {
   // ... whose filter reads no column (docId bitsets / ranges / constants only): the select pass
   // evaluates the CNF on 64-doc words
   bool word_select = false;
-  int wsel_words = 4;  // word-level select: 64-doc words per lane and step (4 or 8; 16 words are one tile)
   int sel_group = 1;   // tile-level select: 1024-doc tiles per loop step (1, 2 or 4; each segment's tile
                        // range in the launch padded to a multiple of it)
   // XCD-aware tile ranges: workgroups are dealt round-robin over the 8 XCDs (b and b + 8 share one), so the
@@ -179,13 +175,6 @@ struct JitPlan {
   // (0: always) -- admission by recurrence, so the slots hold a skewed distribution's head
   int hash_admit = 0;
   int hash_probes = kHashLdsProbes;  // LDS-level slots a doc's key probes before it spills (<= kHashLdsProbes)
-  // diagnostics only (PINOT_AMD_DIAG_ADMIT_OFF): the dense admission's per-doc bitmap lookup left out (wrong
-  // results; isolates the lookup's traffic in A/B profiles)
-  bool diag_admit_off = false;
-  // diagnostics only (PINOT_AMD_DIAG_REC_WRAP = bytes, a power of two): the scatter's flushed records wrap around
-  // a buffer of that many bytes (wrong results; with a small wrap the record writes stay in the Infinity Cache,
-  // which measures what the record round trip through HBM costs the scatter)
-  int64_t diag_rec_wrap = 0;
   // Segment-level safe trim (GroupByOperator.java:157-175 with QueryContext's effective trim size = LIMIT):
   // a dense key K's rank in the ORDER BY order is ord(K) = sum over the ORDER BY columns of id' x ostride,
   // id = (K / stride) % size (the GROUP BY column's merged id), id' = size - 1 - id for DESC. Non-empty: the

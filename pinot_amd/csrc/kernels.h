@@ -1,0 +1,100 @@
+// kernels.h — the host-callable launchers of kernels.hip and derive.hip. host.cpp and both definition files
+// include this, so the compiler checks each definition against the one declaration.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "device_types.h"
+
+namespace pamd {
+// kernels.hip
+hipError_t launch_init_acc(uint64_t* d_acc, const DevQuery& q, int64_t num_keys, hipStream_t st);
+hipError_t launch_sext_hi(uint64_t* d_acc, int64_t n, const int32_t* arrs, int32_t narr, hipStream_t st);
+hipError_t launch_raw_int_minmax(const uint8_t* be, int type, int64_t n, long long* out, hipStream_t st);
+hipError_t launch_fingerprint(const void* p, size_t bytes, unsigned long long* out, hipStream_t st);
+hipError_t launch_for_pack(const uint8_t* be, int type, int64_t n, unsigned long long base, int lo_bits, int hi_bits,
+                           uint8_t* lo, uint8_t* hi, hipStream_t st);
+hipError_t launch_trim(const unsigned long long* keys, int64_t cap, int nw_seg, const uint64_t* acc, int fd_acc,
+                       int32_t nsegs, int64_t limit, const int64_t* bucket_base, uint32_t* hist,
+                       unsigned long long* seg_distinct, int64_t* bstar, int64_t* rank, unsigned long long* bitmap,
+                       int64_t* dstar, unsigned long long* limit_reached, hipStream_t st);
+hipError_t launch_hash_merge(const unsigned long long* skeys, int64_t scap, int nw, int has_seg, const uint64_t* sacc,
+                             unsigned long long* fkeys, int64_t fcap, uint64_t* facc, const DevQuery& q, int fd_acc,
+                             const int64_t* dstar, unsigned long long* overflow, hipStream_t st,
+                             const SegSelStage* sst = nullptr, int nst = 0, const int32_t* sdone = nullptr,
+                             const uint64_t* scut = nullptr);
+hipError_t launch_segsel(const unsigned long long* keys, int64_t cap, int nw, const uint64_t* acc, int fd_acc,
+                         const int64_t* dstar, const DevQuery& q, const SegSelStage* sst, int nst, int32_t nsegs,
+                         int64_t keep, unsigned long long* cnt, int64_t* want, int32_t* done, uint64_t* prefix,
+                         uint64_t* cut, uint32_t* hist, hipStream_t st);
+hipError_t launch_admit(uint32_t* first, int64_t nk, const uint32_t* seen, const unsigned long long* seen_n, int64_t cap,
+                        int32_t nsegs, int64_t limit, const int64_t* bucket_base, int64_t max_buckets, uint32_t* hist,
+                        int64_t* bstar, int64_t* rank, unsigned long long* bitmap, int64_t* dstar,
+                        unsigned long long* limit_reached, int phase, uint32_t* admit, int64_t words, hipStream_t st);
+hipError_t launch_presence_bitset(const uint64_t* count, int64_t n, unsigned long long* bits, hipStream_t st);
+hipError_t launch_seg_cut(const unsigned long long* bits, int64_t words, int32_t nsegs, int64_t limit,
+                          unsigned long long* cut, hipStream_t st);
+hipError_t launch_spill_direct_prep(const int64_t* offs, const int64_t* part_begin, const uint32_t* hist, int P,
+                                    int64_t grid, int64_t* dbase, uint32_t* dcnt, int64_t* pbeg, hipStream_t st);
+hipError_t launch_spill_agg(const DevHash& H, int nw, const unsigned long long* sorted, const int64_t* part_begin,
+                            const DevQuery& q, uint64_t* acc, int agg_grid, int S, uint32_t narrow, hipStream_t st);
+hipError_t launch_spill_passes(const DevHash& H, int nw, int64_t grid, const uint32_t* hist_unused, int64_t* offs,
+                               int64_t* part_begin, unsigned long long* sorted, const DevQuery& q, uint64_t* acc,
+                               int agg_grid, int S, int sorted_scatter, uint32_t narrow, hipStream_t st);
+hipError_t launch_gather_groups(const int32_t* slots, int64_t ngroups, const unsigned long long* keys, int nw,
+                                int64_t cap, const uint64_t* acc, int32_t nacc, uint64_t* out_keys, uint64_t* out_acc,
+                                hipStream_t st);
+hipError_t launch_export_groups(const int32_t* slots, int64_t ngroups, const unsigned long long* hkeys, int64_t cap,
+                                const uint64_t* acc, int32_t nacc_out, const DevKeyPack& kp, uint64_t* out_keys,
+                                uint64_t* out_acc, hipStream_t st);
+hipError_t launch_merge_rows(const uint64_t* keys, const uint64_t* acc, int64_t n, int nw, int nacc_in,
+                             unsigned long long* fkeys, int64_t fcap, uint64_t* facc, const DevQuery& q,
+                             unsigned long long* overflow, hipStream_t st);
+hipError_t launch_distinct_fold_count(const uint64_t* ckeys, int64_t nrows, const DevKeyPack& kc, const DevKeyPack& kb,
+                                      const uint64_t* bkeys, int64_t nbase, int cbits, uint32_t* cnt, uint64_t* pair,
+                                      unsigned long long* miss, hipStream_t st);
+hipError_t launch_distinct_fold_fill(const uint64_t* sorted, int64_t nrows, int cbits, const uint32_t* cnt, int64_t nbase,
+                                     int64_t* off, int32_t* values, hipStream_t st);
+hipError_t launch_value_count_scan(const uint64_t* counts, int64_t n, int64_t* bsum, int64_t* cum, hipStream_t st);
+hipError_t launch_percentile_select(const int64_t* off, const int64_t* cum, const int32_t* values, int64_t ngroups,
+                                    const double* pct, int np, int32_t* out, hipStream_t st);
+int64_t distinct_fold_sum_tiles(int64_t nrows);
+hipError_t launch_distinct_fold_sum(const uint64_t* sorted, int64_t nrows, int cbits, const int64_t* off, int64_t nbase,
+                                    const double* dictd, const int64_t* dicti, double* sumd, uint64_t* sumi,
+                                    double* partd, uint64_t* parti, hipStream_t st);
+hipError_t launch_read_dict_ids(const uint8_t* packed, int bits, int64_t start, int64_t len, int32_t* out,
+                                hipStream_t st);
+hipError_t launch_pack_dict_ids(const int32_t* values, int64_t n, int bits, uint8_t* packed, hipStream_t st);
+hipError_t launch_read_raw(const uint8_t* raw, int type, int64_t start, int64_t len, uint8_t* out, hipStream_t st);
+hipError_t launch_chunk_decompress(const uint8_t* src, uint8_t* dst, const void* jobs, int32_t njobs, int32_t* status,
+                                   hipStream_t st);
+hipError_t launch_bitset_binop(const uint64_t* a, const uint64_t* b, uint64_t* out, int64_t n, int op,
+                               hipStream_t st);
+hipError_t launch_bitset_not(const uint64_t* a, uint64_t* out, int64_t num_docs, hipStream_t st);
+int64_t compact_num_chunks(int64_t num_docs);
+hipError_t launch_bitset_count(const uint64_t* bits, int64_t num_docs, int64_t* d_chunk_counts, int64_t* d_total,
+                               hipStream_t st);
+hipError_t launch_bitset_compact(const uint64_t* bits, int64_t num_docs, const int64_t* d_chunk_offsets,
+                                 int32_t* out, hipStream_t st);
+hipError_t launch_expand_jobs(const void* d_jobs, int32_t njobs, int64_t total_items, hipStream_t st);
+hipError_t launch_roaring_select(const void* d_jobs, const void* d_fs, int32_t nfs, int64_t total_items, const void* d_segs,
+                                 int32_t nleaves, int32_t nclauses, unsigned long long* sel_entries,
+                                 unsigned long long* sel_count, int64_t sel_cap, unsigned long long* matched_out, int clause,
+                                 hipStream_t st);
+hipError_t launch_pack_sel(const void* conts, const int32_t* sel, int64_t n, int group, unsigned long long* out,
+                           hipStream_t st);
+int expand_group();
+hipError_t launch_partition_offsets(const uint32_t* d_hist, int32_t nparts, int64_t nblocks, int64_t* d_offs,
+                                    int64_t* d_part_begin, hipStream_t st);
+hipError_t launch_allot_prefix(const uint32_t* d_hist, int32_t P, int64_t G, int mode, int64_t stride, double scale,
+                               int64_t limit, int64_t* d_ptot, int64_t* d_out, hipStream_t st);
+
+// derive.hip
+size_t derive_dictionary_scratch(int64_t n);
+hipError_t derive_dictionary(const uint8_t* d_be, int type, int64_t n, void* d_scratch, int32_t* d_ids,
+                             uint8_t* d_dict_be, int64_t* h_card, hipStream_t st);
+size_t sort_rows_scratch(int64_t n);
+hipError_t sort_rows_by_key(const uint64_t* keys, int nwk, const int* word_bits, const uint64_t* acc, int nacc, int64_t n,
+                            void* scratch, uint64_t* keys_out, uint64_t* acc_out, hipStream_t st);
+}  // namespace pamd

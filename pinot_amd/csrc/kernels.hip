@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "device_types.h"
+#include "kernels.h"
 #include "../../include/pinot_amd.h"
 
 namespace pamd {
@@ -1764,9 +1765,9 @@ __global__ void __launch_bounds__(kBlock) roaring_select_kernel(const ExpandJob*
 }
 
 // The same selection with a clause's non-negated bitset leaves expanded together into the LDS region (the
-// expansion ORs) and only the match words live across the expansion. The default for filters without
-// negated bitset leaves (5-9 % faster than the per-leaf fold at 0.01-0.1 %); PINOT_AMD_FUSED_VARIANT=leaf
-// forces the per-leaf kernel above.
+// expansion ORs) and only the match words live across the expansion. Used for filters without
+// negated bitset leaves (5-9 % faster than the per-leaf fold at 0.01-0.1 %); the others take the per-leaf
+// kernel above.
 template <int G>
 __global__ void __launch_bounds__(kBlock) roaring_select_clause_kernel(const ExpandJob* jobs, const FusedSelSeg* fs,
                                                                       int32_t nfs, int64_t total_items,
@@ -2570,18 +2571,7 @@ hipError_t launch_pack_sel(const void* conts, const int32_t* sel, int64_t n, int
 // the chunk-group size (1, 2, 4 or 8 chunks per work item; the planner groups the containers the same way).
 // Swept on configs[2] (profiles/r03/sweep_inv_expand_group.txt): 4 beats 8 (a 64 KiB LDS bitset halves
 // the blocks per CU) and 1 (every small container its own line fetch)
-int expand_group() {
-#ifdef PINOT_AMD_DIAGNOSTICS  // the sweep's knob (diagnostics builds only)
-  static const int g = [] {
-    const char* e = getenv("PINOT_AMD_EXPAND_GROUP");
-    const int v = e ? atoi(e) : 4;
-    return v >= 8 ? 8 : v >= 4 ? 4 : v >= 2 ? 2 : 1;
-  }();
-  return g;
-#else
-  return 4;
-#endif
-}
+int expand_group() { return 4; }
 
 hipError_t launch_roaring_select(const void* d_jobs, const void* d_fs, int32_t nfs, int64_t total_items, const void* d_segs,
                                  int32_t nleaves, int32_t nclauses, unsigned long long* sel_entries,

@@ -1,6 +1,6 @@
 # A/B PMC passes: for each case (label, env settings, bench args) one short bench run per counter set
 # (rocprofv3 does not split counters over passes), then per-kernel means per dispatch for every case.
-#   CASES="base||--workload highcard-default --segments 40;off|PINOT_AMD_DIAG_ADMIT_OFF=1|--workload highcard-default --segments 40" \
+#   CASES="base||--workload highcard-default --segments 40;seq|PINOT_AMD_ADMIT_SEQ=0|--workload highcard-default --segments 40" \
 #   SETS="FETCH_SIZE;WRITE_SIZE;TCC_HIT_sum TCC_MISS_sum" bash scripts/pmc_ab.sh > gpurun_out/ab.txt
 set -o pipefail
 export TMPDIR=/tmp
