@@ -2,8 +2,8 @@
  * pinot_amd.h — C ABI of the MI355X segment-execution library (libpinot_amd.so).
  *
  * This is the drop-in boundary for Pinot's server-side segment execution hot path:
- * forward-index scan, filter (scan + inverted index), aggregation and group-by over
- * immutable segments staged in HBM. Every entry point takes plain pointers and sizes
+ * forward-index scan, filter (scan + inverted index), aggregation, group-by and selection
+ * (SELECT columns [ORDER BY ...] LIMIT n) over immutable segments staged in HBM. Every entry point takes plain pointers and sizes
  * (no torch or Java types), so a JNI / Panama FFM binding in pinot-core can call it
  * directly; INTEGRATION.md shows the Java-side binding.
  *
@@ -276,6 +276,52 @@ int pinot_amd_query_set_segment_trim(pinot_amd_query* q, int64_t min_segment_gro
 int pinot_amd_query_add_order_by(pinot_amd_query* q, int32_t kind, int32_t index, int32_t ascending);
 
 /* ------------------------------------------------------------------------------------------------
+ * Selection queries: SELECT a, b FROM t WHERE ... [ORDER BY c DESC, ...] LIMIT n [OFFSET m]
+ * (core/plan/SelectionPlanNode.java -> core/operator/query/SelectionOnlyOperator.java /
+ * SelectionOrderByOperator.java per segment -> core/operator/combine/SelectionOrderByCombineOperator.java).
+ * A query with at least one selection column is a selection query: pinot_amd_execute runs the filter and, in the
+ * same pass, keeps each segment's best offset + limit rows on the device (SelectionOrderByOperator.java:112: the
+ * server keeps offset + limit rows, the broker applies the offset), gathers their columns by docId
+ * (SelectionOrderByOperator.java:270-330, the second-round projection) and combines the segments' rows.
+ *   - Columns: plain single-value columns of any stored type, STRING included. The result's columns are the
+ *     selection columns in the order added; the caller arranges them into the server's schema -- the ORDER BY
+ *     columns first (core/query/selection/SelectionOperatorUtils.java:83-125) -- and expands SELECT *.
+ *   - ORDER BY compares by value: INT / LONG numerically, FLOAT / DOUBLE as Float.compare / Double.compare
+ *     (-0.0 < 0.0, NaN greatest), STRING as String.compareTo; descending reverses it. Pinot leaves ties unspecified
+ *     (SelectionOperatorUtils.java:630-637 evicts an arbitrary worst row; the combine is multi-threaded): here ties
+ *     are broken by ascending (index of the segment in the batch, docId), one of Pinot's possible answers, so
+ *     results are deterministic. The key is at most two 64-bit words (a dictionary column, INT or FLOAT takes 32
+ *     bits, a raw LONG or DOUBLE 64): a wider ORDER BY is EUNSUPPORTED.
+ *   - Without ORDER BY the rows are the first offset + limit matching docs in (segment index, docId) order
+ *     (SelectionOnlyOperator takes docs in docId order; Pinot's combine takes whichever segments answer first).
+ *     Segments are scanned in batch order in groups of 1, 2, 4, ... and the scan stops once enough rows are held.
+ *   - LIMIT 0: the ORDER BY is ignored and no row is returned (EmptySelectionOperator); the schema is valid.
+ *   - offset + limit up to half the scan's LDS buffer (2048 rows without ORDER BY, 1024 with) is pruned on the
+ *     device as it scans (kernel_info "jit-topk"); above that every matching doc's record is written and sorted
+ *     ("jit-topk-sort"), within PINOT_AMD_TOPK_SORT_MAX_BYTES (default 4 GiB) and offset + limit <= 2^20, beyond
+ *     which the query is EUNSUPPORTED.
+ * A query with selection columns and any aggregation or GROUP BY fails pinot_amd_execute with EINVAL;
+ * pinot_amd_execute_filter ignores the selection fields.
+ *
+ * The result calls on a selection result:
+ *   pinot_amd_result_num_docs_matched   with ORDER BY every matching doc; without, the rows returned
+ *   pinot_amd_execute_again             re-runs the passes; last_kernel_ms covers them (the scan, the candidate
+ *                                       sort, the cut and the gather)
+ *   kernel_info                         "jit-topk" or "jit-topk-sort", " xN" for N launches run
+ *   algorithmic_bytes                   the filter and ORDER BY columns streamed once, plus the gathered columns of
+ *                                       the rows fetched
+ *   check_word                          reads 0
+ *   num_groups, fetch, fetch_intermediate, fetch_distinct_values, fetch_value_counts: EINVAL
+ *   accumulators, export_groups, merge_groups: EUNSUPPORTED
+ * --------------------------------------------------------------------------------------------- */
+/* An output column; out_index (optional) receives its index among the result's columns. */
+int pinot_amd_query_add_selection(pinot_amd_query* q, const char* column, int32_t* out_index);
+/* An ORDER BY column, in order of precedence (ascending != 0 for ASC); it need not be selected. */
+int pinot_amd_query_add_selection_order_by(pinot_amd_query* q, const char* column, int32_t ascending);
+/* LIMIT and OFFSET, both >= 0 (EINVAL otherwise). Not set: LIMIT 10 (Pinot's default), OFFSET 0. */
+int pinot_amd_query_set_selection_limit(pinot_amd_query* q, int64_t limit, int64_t offset);
+
+/* ------------------------------------------------------------------------------------------------
  * Execution and results (IntermediateResultsBlock / AggregationGroupByResult equivalents).
  * --------------------------------------------------------------------------------------------- */
 typedef struct pinot_amd_result pinot_amd_result;
@@ -413,10 +459,27 @@ int pinot_amd_result_fetch_value_counts(pinot_amd_result* r, int32_t agg_index, 
  * not a STRING column or id is out of range). */
 const char* pinot_amd_result_distinct_string(pinot_amd_result* r, int32_t agg_index, int64_t id);
 
+/* Selection results (DataSchema + rows of SelectionResultsBlock). EINVAL on any other result. */
+int pinot_amd_result_selection_num_columns(pinot_amd_result* r, int32_t* h_out);
+/* Column j's name (owned by the result) and stored type (pinot_amd_data_type); either out pointer may be NULL. */
+int pinot_amd_result_selection_column(pinot_amd_result* r, int32_t j, const char** h_name, int32_t* h_stored_type);
+/* Rows of the last execution: at most offset + limit. */
+int pinot_amd_result_num_rows(pinot_amd_result* r, int64_t* h_out);
+/* The rows in result order: h_values[row * num_columns + j] encoded as pinot_amd_result_fetch encodes keys -- the
+ * value as int64 (INT / LONG), its double bits (DOUBLE; a FLOAT widened to double), or an id for
+ * pinot_amd_result_selection_string (STRING). h_segment / h_doc_id (optional) receive each row's origin: the
+ * index of its segment in the batch and its docId. More rows than cap: EOVERFLOW. */
+int pinot_amd_result_fetch_rows(pinot_amd_result* r, int64_t cap, int32_t* h_segment, int32_t* h_doc_id, int64_t* h_values,
+                                int64_t* h_num_fetched);
+/* String of id `id` of STRING column j of the fetched rows (NULL when out of range); valid until the next
+ * execution of the result. */
+const char* pinot_amd_result_selection_string(pinot_amd_result* r, int32_t j, int64_t id);
+
 /* The device plan: "jit" (fused scan), "jit-partitioned", "jit-hash", "jit-hash-trim"; then "-select" /
  * "-wselect" / "-fwselect" for a selection-vector plan (filter on 4-doc tiles / on 64-doc bitset words /
  * fused with the inverted-index expansion), "+admit-seq" / "+admit" for numGroupsLimit admission
- * (sequential / first-doc), and " xN" when the batch ran as N shape launches. */
+ * (sequential / first-doc), and " xN" when the batch ran as N shape launches; "jit-topk" /
+ * "jit-topk-sort" for a selection query. */
 const char* pinot_amd_result_kernel_info(pinot_amd_result* r);
 /* Algorithmic HBM bytes of the last execution (the roofline numerator): every decoded column once
  * (fixed-bit columns at their bit width, raw columns at their value width, or at their packed twin's width

@@ -271,6 +271,23 @@ struct DevQuery {
   const unsigned long long* seg_cut;
   unsigned long long* seg_bits;
   int64_t seg_words;
+  // selection top-K (JitPlan::topk): candidate records of tk_words 64-bit words each, appended with one
+  // reservation per block flush. tk_count[0] = records reserved, tk_count[1] = flushes that found no room below
+  // tk_cap (the result then fails). tk_k: the rows each segment keeps (offset + limit; the pruning scan's
+  // threshold rank)
+  unsigned long long* tk_rec;
+  unsigned long long* tk_count;
+  int64_t tk_cap;
+  int32_t tk_k;
+  int32_t tk_pad;
+};
+
+// Selection: one (segment, result column) of the second-round projection over the surviving rows
+// (selection_gather_kernel): the forward index read by docId, numeric dictionaries looked up on the device
+struct SelCol {
+  const uint8_t* data;  // FIXED_BIT: BE bit stream | RAW: BE values | SORTED: LE int32 start docId per dictId
+  const void* dict;     // LE dictionary values (numeric dictionary columns), null for STRING
+  int32_t enc, type, bits, card;
 };
 
 }  // namespace pamd

@@ -104,6 +104,9 @@ static const std::set<std::string>& kept_knobs() {
       "PINOT_AMD_DENSE_MAX_KEYS",
       "PINOT_AMD_PLAN_CACHE",
       "PINOT_AMD_PLAN_CACHE_BYTES",
+      "PINOT_AMD_TOPK_BLOCKS",
+      "PINOT_AMD_TOPK_LDS_ROWS",
+      "PINOT_AMD_TOPK_SORT_MAX_BYTES",
   };
   return kept;
 }
@@ -1249,6 +1252,12 @@ struct pinot_amd_query {
   int server_final = 0;
   int64_t sort_agg_threshold = 10000;
   int64_t min_seg_trim = -1;  // minSegmentGroupTrimSize
+  // selection (SelectionPlanNode): the output columns in select-list order, the ORDER BY columns (they need not be
+  // selected), LIMIT (Pinot's default 10) and OFFSET; a query with output columns is a selection query
+  std::vector<std::string> sel_cols;
+  struct SelOrder { std::string column; int asc; };
+  std::vector<SelOrder> sel_order;
+  int64_t sel_limit = 10, sel_offset = 0;
 };
 
 extern "C" {
@@ -1423,6 +1432,26 @@ int pinot_amd_query_add_order_by(pinot_amd_query* q, int32_t kind, int32_t index
   if (kind == 1 && index >= (int32_t)q->aggs.size())
     return fail(PINOT_AMD_EINVAL, "add_order_by: aggregation %d not in the query", index);
   q->order_by.push_back({kind, index, ascending ? 1 : 0});
+  return 0;
+}
+
+int pinot_amd_query_add_selection(pinot_amd_query* q, const char* column, int32_t* out_index) {
+  if (!q || !column || !*column) return fail(PINOT_AMD_EINVAL, "add_selection: bad arguments");
+  if (out_index) *out_index = (int32_t)q->sel_cols.size();
+  q->sel_cols.push_back(column);
+  return 0;
+}
+
+int pinot_amd_query_add_selection_order_by(pinot_amd_query* q, const char* column, int32_t ascending) {
+  if (!q || !column || !*column) return fail(PINOT_AMD_EINVAL, "add_selection_order_by: bad arguments");
+  q->sel_order.push_back({column, ascending ? 1 : 0});
+  return 0;
+}
+
+int pinot_amd_query_set_selection_limit(pinot_amd_query* q, int64_t limit, int64_t offset) {
+  if (!q || limit < 0 || offset < 0) return fail(PINOT_AMD_EINVAL, "set_selection_limit: bad arguments");
+  q->sel_limit = limit;
+  q->sel_offset = offset;
   return 0;
 }
 
@@ -1667,6 +1696,30 @@ struct pinot_amd_result {
   int32_t n_sext = 0;
   int64_t ngroups = 0;
   std::vector<uint64_t> ckeys, cacc;  // per group: key words (hash) or dense key; all accumulator words
+  // Selection (run_selection): the top-K scan's candidate records (tk_rec, sel_words words each, sel_cap of them)
+  // and their sorted copy, each segment's kept rows (row_seg / row_doc) and their gathered columns (tk_vals), then
+  // the combine on the host over those rows. Gathered columns: the selected ones in select-list order, then the
+  // ORDER BY columns not among them; sel_keys names the ORDER BY among the gathered columns.
+  bool topk = false;
+  bool sel_prune = true;   // rows pruned in LDS (jit-topk), or every matching doc's record sorted (jit-topk-sort)
+  int sel_words = 1;
+  int64_t sel_k = 0;       // offset + limit
+  int64_t sel_cap = 0;
+  int sel_nout = 0;        // selected columns (the result's columns)
+  std::vector<std::string> sel_names;
+  std::vector<int32_t> sel_types;
+  struct SelKey { int col, asc; };
+  std::vector<SelKey> sel_keys;
+  std::vector<pinot_amd_segment*> sel_segs;  // (a prepared plan is dropped with any of its segments)
+  int sel_ngroups = 0;     // no ORDER BY: the launch groups (1, 2, 4, ... segments in batch order)
+  int sel_groups_run = 0;  // ... and how many of them the last execution launched
+  DevBuf tk_rec, tk_sorted, tk_scratch, tk_ctr, tk_cnt, tk_off, tk_rseg, tk_rdoc, tk_vals, d_selcols;
+  double sel_key_bytes = 0;  // bytes per row of the gathered columns
+  // the last execution's rows
+  int64_t sel_matched = 0, sel_nrows = 0;
+  std::vector<int32_t> row_seg, row_doc;
+  std::vector<int64_t> row_vals;                        // sel_nrows x sel_nout (fetch's key encoding)
+  std::vector<std::vector<std::string>> row_strings;    // per selected STRING column: the kept rows' strings by id
   ~pinot_amd_result() {
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
@@ -1767,6 +1820,15 @@ static std::string plan_identity(const pinot_amd_query& Q, const std::vector<pin
   for (long long v : {(long long)Q.num_groups_limit, (long long)Q.limit, (long long)Q.min_trim, (long long)Q.trim_threshold,
                       (long long)Q.server_final, (long long)Q.sort_agg_threshold, (long long)Q.min_seg_trim})
     num(v);
+  if (!filter_only) {  // (pinot_amd_execute_filter ignores the selection fields)
+    k += "|T";
+    for (const std::string& c : Q.sel_cols) k += c + '\x1f';
+    k += "|";
+    for (const auto& o : Q.sel_order) k += o.column + (o.asc ? "+" : "-") + '\x1f';
+    k += "|";
+    num(Q.sel_limit);
+    num(Q.sel_offset);
+  }
   k += "|S";
   for (auto* sg : segs) k += std::to_string(sg->uid) + "." + std::to_string(sg->gen) + ",";
   int dev = 0;
@@ -2655,7 +2717,162 @@ static int grow_hash(pinot_amd_result* r, bool* grown) {
   return 0;
 }
 
+static int java_double_compare(double a, double b);
+static int read_counters(pinot_amd_result* r, std::vector<unsigned long long>* c);
+
+// A selection query's execution (SelectionOnlyOperator / SelectionOrderByOperator per segment, then
+// SelectionOrderByCombineOperator): the top-K scan over every launch -- with no ORDER BY the launch groups of 1, 2,
+// 4, ... segments in batch order, the matching docs read back between groups, until offset + limit rows are held --
+// then the candidate records sorted by (segment, key, docId), each segment's first offset + limit rows cut, their
+// columns gathered by docId, and the combine on the host over those rows: by value (INT / LONG numerically, FLOAT /
+// DOUBLE as Double.compare, STRING as String.compareTo, DESC reversed), ties by ascending (segment, docId).
+static int run_selection(pinot_amd_result* r) {
+  hipStream_t st = r->stream;
+  r->compacted = false;
+  r->sel_nrows = r->sel_matched = 0;
+  r->sel_groups_run = 0;
+  r->row_seg.clear();
+  r->row_doc.clear();
+  r->row_vals.clear();
+  r->row_strings.assign((size_t)r->sel_nout, {});
+  HIP_OK(hipEventRecord(r->ev0, st));
+  const int64_t K = r->sel_k;
+  const size_t nl = r->launches.size();
+  const int n = (int)r->sel_segs.size(), ncols = (int)r->sel_names.size(), W = r->sel_words;
+  HIP_OK(hipMemsetAsync(r->matched.p, 0, r->matched.n, st));
+  if (K == 0) {  // LIMIT 0 (EmptySelectionOperator): the schema, no row, nothing scanned
+    HIP_OK(hipEventRecord(r->ev1, st));
+    return 0;
+  }
+  if (!r->inv_leaves.empty())
+    HIP_OK(launch_expand_jobs(r->d_expand_jobs.p, (int32_t)r->inv_leaves.size(), r->expand_total, st));
+  HIP_OK(hipMemsetAsync(r->tk_ctr.p, 0, 16, st));
+  DevHash H{};
+  std::vector<unsigned long long> c;
+  auto matched_total = [&]() {
+    int64_t t = 0;
+    for (size_t li = 0; li < nl; ++li) t += (int64_t)c[3 * li];
+    return t;
+  };
+  if (r->sel_keys.empty()) {
+    for (int g = 0; g < r->sel_ngroups; ++g) {
+      for (size_t li = 0; li < nl; ++li)
+        if (r->launches[li].batch == g)
+          if (int rc = launch_one(r, r->launches[li], li, nullptr, H)) return rc;
+      ++r->sel_groups_run;
+      if (int rc = read_counters(r, &c)) return rc;
+      if (matched_total() >= K) break;
+    }
+  } else {
+    for (size_t li = 0; li < nl; ++li)
+      if (int rc = launch_one(r, r->launches[li], li, nullptr, H)) return rc;
+  }
+  unsigned long long ctr[2] = {0, 0};
+  HIP_OK(hipMemcpyAsync(ctr, r->tk_ctr.p, 16, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  if (ctr[1] != 0 || (int64_t)ctr[0] > r->sel_cap) {
+    HIP_OK(hipEventRecord(r->ev1, st));
+    return fail(PINOT_AMD_EOVERFLOW, "selection: %llu candidate records exceed the array's %lld", ctr[0], (long long)r->sel_cap);
+  }
+  const int64_t ncand = (int64_t)ctr[0];
+  int64_t total = 0;
+  std::vector<uint32_t> h_seg, h_doc;
+  std::vector<int64_t> h_vals;
+  if (ncand > 0) {
+    const std::vector<int> bits((size_t)W, 64);
+    HIP_OK(sort_rows_by_key((const uint64_t*)r->tk_rec.p, W, bits.data(), nullptr, 0, ncand, r->tk_scratch.p,
+                            (uint64_t*)r->tk_sorted.p, nullptr, st));
+    HIP_OK(hipMemsetAsync(r->tk_cnt.p, 0, (size_t)n * 4, st));
+    HIP_OK(launch_selection_count((const uint64_t*)r->tk_sorted.p, W, ncand, K, n, (uint32_t*)r->tk_cnt.p, st));
+    std::vector<uint32_t> cnt((size_t)n);
+    HIP_OK(hipMemcpyAsync(cnt.data(), r->tk_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    std::vector<int64_t> off((size_t)n);
+    for (int si = 0; si < n; ++si) {
+      off[si] = total;
+      total += cnt[si];
+    }
+    if ((size_t)total * 4 > r->tk_rseg.n) return fail(PINOT_AMD_EINVAL, "internal: selection kept %lld rows", (long long)total);
+    HIP_OK(hipMemcpyAsync(r->tk_off.p, off.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(launch_selection_cut((const uint64_t*)r->tk_sorted.p, W, ncand, K, n, (const int64_t*)r->tk_off.p, total,
+                                (uint32_t*)r->tk_rseg.p, (uint32_t*)r->tk_rdoc.p, st));
+    HIP_OK(launch_selection_gather((const SelCol*)r->d_selcols.p, ncols, (const uint32_t*)r->tk_rseg.p,
+                                   (const uint32_t*)r->tk_rdoc.p, total, (int64_t*)r->tk_vals.p, st));
+    HIP_OK(hipEventRecord(r->ev1, st));
+    h_seg.resize((size_t)total);
+    h_doc.resize((size_t)total);
+    h_vals.resize((size_t)total * ncols);
+    HIP_OK(hipStreamSynchronize(st));  // (off was read by the copy above)
+    if (total > 0) {
+      HIP_OK(hipMemcpy(h_seg.data(), r->tk_rseg.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+      HIP_OK(hipMemcpy(h_doc.data(), r->tk_rdoc.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+      HIP_OK(hipMemcpy(h_vals.data(), r->tk_vals.p, (size_t)total * ncols * 8, hipMemcpyDeviceToHost));
+    }
+  } else {
+    HIP_OK(hipEventRecord(r->ev1, st));
+  }
+  // the combine: the best offset + limit rows of the segments' rows
+  std::vector<std::vector<const Column*>> kcol(r->sel_keys.size());
+  for (size_t k = 0; k < r->sel_keys.size(); ++k)
+    for (int si = 0; si < n; ++si) kcol[k].push_back(r->sel_segs[si]->cols.at(r->sel_names[r->sel_keys[k].col]).get());
+  auto before = [&](int64_t a, int64_t b) {
+    for (size_t k = 0; k < r->sel_keys.size(); ++k) {
+      const int j = r->sel_keys[k].col, t = r->sel_types[j];
+      const int64_t va = h_vals[(size_t)a * ncols + j], vb = h_vals[(size_t)b * ncols + j];
+      int cmp = 0;
+      if (t == T_STRING) {
+        const std::string& sa = kcol[k][h_seg[a]]->dict_s.at((size_t)va);
+        const std::string& sb = kcol[k][h_seg[b]]->dict_s.at((size_t)vb);
+        cmp = java_less(sa, sb) ? -1 : java_less(sb, sa) ? 1 : 0;
+      } else if (is_float(t)) {
+        double da, db;
+        memcpy(&da, &va, 8);
+        memcpy(&db, &vb, 8);
+        cmp = java_double_compare(da, db);
+      } else {
+        cmp = va < vb ? -1 : va > vb ? 1 : 0;
+      }
+      if (cmp != 0) return r->sel_keys[k].asc ? cmp < 0 : cmp > 0;
+    }
+    if (h_seg[a] != h_seg[b]) return h_seg[a] < h_seg[b];
+    return h_doc[a] < h_doc[b];
+  };
+  std::vector<int64_t> idx((size_t)total);
+  for (int64_t i = 0; i < total; ++i) idx[(size_t)i] = i;
+  const int64_t keep = std::min<int64_t>(K, total);
+  std::partial_sort(idx.begin(), idx.begin() + keep, idx.end(), before);
+  r->sel_nrows = keep;
+  std::vector<std::map<std::pair<uint32_t, int64_t>, int64_t>> ids((size_t)r->sel_nout);
+  for (int64_t i = 0; i < keep; ++i) {
+    const int64_t x = idx[(size_t)i];
+    r->row_seg.push_back((int32_t)h_seg[x]);
+    r->row_doc.push_back((int32_t)h_doc[x]);
+    for (int j = 0; j < r->sel_nout; ++j) {
+      int64_t v = h_vals[(size_t)x * ncols + j];
+      if (r->sel_types[j] == T_STRING) {  // the kept rows' strings, from the segment's host dictionary
+        auto ins = ids[j].emplace(std::make_pair(h_seg[x], v), (int64_t)r->row_strings[j].size());
+        if (ins.second) r->row_strings[j].push_back(r->sel_segs[h_seg[x]]->cols.at(r->sel_names[j])->dict_s.at((size_t)v));
+        v = ins.first->second;
+      }
+      r->row_vals.push_back(v);
+    }
+  }
+  if (int rc = read_counters(r, &c)) return rc;
+  // numDocsScanned: every matching doc under an ORDER BY; without one the rows returned (SelectionOnlyOperator stops)
+  r->sel_matched = r->sel_keys.empty() ? keep : matched_total();
+  return 0;
+}
+
 static int run_plan(pinot_amd_result* r) {
+  if (r->topk) {
+    try {  // (execute_again reaches this outside the ABI's exception guard)
+      return run_selection(r);
+    } catch (const std::bad_alloc&) {
+      return fail(PINOT_AMD_ENOMEM, "selection: host allocation failed");
+    } catch (const std::exception& e) {
+      return fail(PINOT_AMD_EINVAL, "selection: %s", e.what());
+    }
+  }
   r->merged = false;
   r->check_failed = false;
   r->direct_ran = false;
@@ -2976,10 +3193,12 @@ struct PlanBuild {
   int32_t n = 0;
   void* stream = nullptr;
   bool filter_only = false;
+  bool sel = false;  // a selection query: the top-K scan instead of an aggregation
   pinot_amd_result* r = nullptr;
   // the effective query (raw_keys)
   pinot_amd_query filter_q;  // FilterPlanNode only: no projection, no aggregation
   pinot_amd_query raw_gb_q;  // group-by columns redirected to the derived dictionary of raw columns
+  pinot_amd_query sel_q;     // a selection with LIMIT 0: without its ORDER BY (EmptySelectionOperator)
   const pinot_amd_query* Qp = nullptr;
   // slots and leaves (leaves)
   std::vector<std::string> slot_cols;
@@ -3037,6 +3256,7 @@ struct PlanBuild {
   int group_launches();
   int plan_launches();
   int alloc_buffers();
+  int selection_buffers();
 
   int plan_launch(size_t li);
   int launch_segments(LaunchBuild& lb);
@@ -3051,6 +3271,11 @@ struct PlanBuild {
 int PlanBuild::raw_keys() {
   if (filter_only) filter_q.preds = qq->preds;  // FilterPlanNode only: no projection, no aggregation
   Qp = filter_only ? &filter_q : qq;
+  if (sel && qq->sel_limit + qq->sel_offset == 0 && !qq->sel_order.empty()) {
+    sel_q = *qq;
+    sel_q.sel_order.clear();
+    Qp = &sel_q;
+  }
   for (size_t j = 0; j < Qp->group_by.size(); ++j) {
     const std::string g = Qp->group_by[j];  // a copy: the redirect below rewrites Qp->group_by[j]
     int nraw = 0;
@@ -3090,6 +3315,8 @@ int PlanBuild::leaves() {
       if (!a.column.empty()) if (int rc = need(a.column)) return rc;
       if (!a.column2.empty()) if (int rc = need(a.column2)) return rc;
     }
+    for (auto& c : Q.sel_cols) if (int rc = need(c)) return rc;
+    for (auto& o : Q.sel_order) if (int rc = need(o.column)) return rc;
   }
   for (auto& g : Q.group_by) slot_of(g);
   for (auto& a : Q.aggs) {
@@ -3104,6 +3331,9 @@ int PlanBuild::leaves() {
     }
   }
 
+  // a selection scan decodes its filter and ORDER BY columns only (the selected ones are gathered by docId)
+  if (sel)
+    for (auto& o : Q.sel_order) slot_of(o.column);
   // ---- per-segment leaves (PredicateEvaluatorProvider per segment) ----
   np = Q.preds.size();
   seg_leaves.assign(n, std::vector<DevLeaf>(np));
@@ -3117,6 +3347,7 @@ int PlanBuild::leaves() {
     const PredSpec& p = Q.preds[pi];
     bool d = std::find(Q.group_by.begin(), Q.group_by.end(), p.column) != Q.group_by.end();
     for (auto& a : Q.aggs) d |= a.column == p.column || a.column2 == p.column;
+    for (int sl = 0; sl < (int)slot_cols.size() && sel; ++sl) d |= slot_cols[sl] == p.column;
     pred_decoded[pi] = d ? 1 : 0;
     pred_key[pi] = leaf_cache_key(p, -1, d);
   }
@@ -3629,6 +3860,20 @@ int PlanBuild::hash_sizes() {
         if ((double)c < 2.0 * 1) return fail(PINOT_AMD_EINVAL, "internal: empty trim batch");
     }
   }
+  if (sel && Q.sel_order.empty()) {
+    // SelectionOnlyOperator stops at LIMIT rows: the segments launch in batch order in groups of 1, 2, 4, ...
+    // (run_selection reads the matching docs back between groups and stops once offset + limit rows are held)
+    int b = 0, left = 1;
+    for (int si = 0; si < n; ++si) {
+      seg_batch[si] = b;
+      if (--left == 0 && si + 1 < n) {
+        ++b;
+        left = 1 << std::min(b, 20);
+      }
+    }
+    r->nbatches = b + 1;
+    r->sel_ngroups = b + 1;
+  }
   return 0;
 }
 
@@ -3861,6 +4106,40 @@ int PlanBuild::kernel_choices() {
   }
   if (!base.lds && !base.partitioned)
     for (JitAcc& a : base.accs) a.narrow = 0;  // HBM tables take full 128-bit adds
+  if (sel) {
+    // The top-K scan: the ORDER BY columns as key fields. LDS buffer: 32 KiB of records for the empty and the
+    // one-word key (4096 / 2048 records), 48 KiB for the two-word key (2048); offset + limit up to half of it is
+    // pruned in LDS, above that every matching doc's record is sorted (PINOT_AMD_TOPK_LDS_ROWS shrinks it: tests)
+    base.topk = true;
+    base.aggregate = false;
+    for (auto& o : Q.sel_order) base.topk_key.push_back({slot_of(o.column), o.asc ? 0 : 1});
+    // every launch writes records of one width into the one candidate array: a key column's field (32 bits for a
+    // dictId, INT or FLOAT, 64 for a raw LONG or DOUBLE) must be as wide in every segment
+    auto field_bits = [](const DevColumn& c) { return (c.enc == ENC_RAW && (c.type == T_LONG || c.type == T_DOUBLE)) ? 64 : 32; };
+    int key_bits = 0;
+    for (auto& f : base.topk_key) {
+      for (int si = 0; si < n; ++si)
+        if (field_bits(hsegs[si].cols[f.slot]) != field_bits(hsegs[0].cols[f.slot]))
+          return fail(PINOT_AMD_EUNSUPPORTED, "ORDER BY column %s is raw in some segments only", slot_cols[f.slot].c_str());
+      key_bits += field_bits(hsegs[0].cols[f.slot]);
+    }
+    if (key_bits > 128)
+      return fail(PINOT_AMD_EUNSUPPORTED, "selection ORDER BY key of %d bits (max two 64-bit words)", key_bits);
+    const int W = (key_bits + 64 + 63) / 64;
+    int rows = W == 1 ? 4096 : 2048;
+    if (const char* e = knob("PINOT_AMD_TOPK_LDS_ROWS")) {
+      int want = std::max(512, std::min(rows, atoi(e)));
+      rows = 512;
+      while (rows * 2 <= want) rows *= 2;
+    }
+    base.topk_rows = rows;
+    const int64_t K = Q.sel_limit + Q.sel_offset;
+    base.topk_prune = K <= rows / 2;
+    if (!base.topk_prune && K > ((int64_t)1 << 20))
+      return fail(PINOT_AMD_EUNSUPPORTED, "selection of offset + limit = %lld rows (max %d)", (long long)K, 1 << 20);
+    r->sel_prune = base.topk_prune;
+    r->sel_words = W;
+  }
   if (r->kind == PLAN_HASH) {
     base.hash = true;
     base.hash_seg = r->trim;
@@ -4061,6 +4340,7 @@ int PlanBuild::select_plan() {
     }
   }
 
+  if (sel) base.sel_group = 1;  // the top-K scan takes one tile per step
   // Hash-table plans (DictionaryBasedGroupKeyGenerator's map-based holders) get an LDS-privatised first
   // level: one CU-wide block (4 x 256 threads) per CU keeps up to S keys with their accumulators in LDS,
   // so repeated keys (skewed group distributions) aggregate on-die and reach the HBM table once per block
@@ -4206,7 +4486,7 @@ int PlanBuild::launch_segments(LaunchBuild& lb) {
   for (int si : L.segs) {
     DevSegment ds = hsegs[si];
     ds.tile_begin = tiles;
-    ds.key_seg = r->admit ? si : key_seg[si];
+    ds.key_seg = (r->admit || sel) ? si : key_seg[si];  // (a selection's records carry the batch's segment index)
     ds.pad = r->admit ? 1 : 0;  // sequential admission over whole segments: each one walked to its end
     // (a tile-level select with G tiles per step: the segment's range padded to a multiple of G; the
     // padding tiles match nothing and read only their columns' staging padding)
@@ -4647,6 +4927,7 @@ int PlanBuild::plan_launch(size_t li) {
       L.shmem_sets += (size_t)(((1 << jl.lut) + 3) / 4) * 4;
     }
   }
+  if (jp.topk) L.shmem = jit_topk_lds(jp);  // the candidate buffer, the filter's tables behind it
   if (!jp.select) L.shmem += L.shmem_sets;  // a select pass has no table: its sets start at 0
   if (L.jit_direct) L.shmem_direct += L.shmem_sets;
   const int per_cu = jp.partitioned ? launch_partitioned(lb)
@@ -4663,6 +4944,8 @@ int PlanBuild::plan_launch(size_t li) {
     grid = std::min<int64_t>(grid, 2 * (int64_t)cus);
     L.shmem_agg += (size_t)(2 * grid + 1) * 8;
   }
+  if (jp.topk)  // (tests: a few blocks walk many tiles, so reductions and segment changes happen inside one block)
+    if (const char* tb = knob("PINOT_AMD_TOPK_BLOCKS")) grid = std::max<int64_t>(1, std::min<int64_t>(grid, atoll(tb)));
   L.grid = (int)grid;
   if (jp.partitioned) max_count_cells = std::max(max_count_cells, (size_t)jp.nparts * (size_t)grid * kPartCountRatio);
   return 0;
@@ -4881,6 +5164,88 @@ int PlanBuild::alloc_buffers() {
   return 0;
 }
 
+// a selection plan's result columns, candidate array, sort scratch and gather descriptors
+int PlanBuild::selection_buffers() {
+  const pinot_amd_query& Q = *Qp;
+  r->topk = true;
+  r->sel_k = Q.sel_limit + Q.sel_offset;
+  r->sel_segs = segs;
+  r->sel_nout = (int)Q.sel_cols.size();
+  r->sel_names = Q.sel_cols;
+  for (auto& o : Q.sel_order) {
+    auto it = std::find(r->sel_names.begin(), r->sel_names.end(), o.column);
+    if (it == r->sel_names.end()) {
+      r->sel_names.push_back(o.column);
+      it = r->sel_names.end() - 1;
+    }
+    r->sel_keys.push_back({(int)(it - r->sel_names.begin()), o.asc});
+  }
+  const int ncols = (int)r->sel_names.size();
+  std::vector<SelCol> sc((size_t)n * ncols);
+  r->sel_key_bytes = 0;
+  for (int j = 0; j < ncols; ++j) {
+    const int32_t t0 = segs[0]->cols.at(r->sel_names[j])->type;
+    r->sel_types.push_back(t0);
+    for (int si = 0; si < n; ++si) {
+      const Column& c = *segs[si]->cols.at(r->sel_names[j]);
+      if (c.type != t0) return fail(PINOT_AMD_EINVAL, "column %s has different types across segments", c.name.c_str());
+      if (c.enc == ENC_RAW && c.type == T_STRING)
+        return fail(PINOT_AMD_EUNSUPPORTED, "selection of raw STRING column %s", c.name.c_str());
+      SelCol& d = sc[(size_t)si * ncols + j];
+      d.data = (const uint8_t*)c.fwd.p;
+      d.dict = c.type == T_STRING ? nullptr : c.dict.p;
+      d.enc = c.enc;
+      d.type = c.type;
+      d.bits = c.bits;
+      d.card = c.card;
+    }
+    const Column& c0 = *segs[0]->cols.at(r->sel_names[j]);
+    r->sel_key_bytes += c0.enc == ENC_RAW ? (double)value_size(c0.type)
+                                          : (c0.enc == ENC_FIXED_BIT ? c0.bits / 8.0 : 0.0) + (c0.type == T_STRING ? 0.0 : value_size(c0.type));
+  }
+  if (int rc = r->d_selcols.alloc_copy(sc.data(), sc.size() * sizeof(SelCol), 0)) return rc;
+  // Candidate records. Pruned: a block flushes at most offset + limit records per segment it walks, and the blocks'
+  // contiguous tile ranges meet at most grid + segments (block, segment) pairs per launch. Sort path: one record per
+  // matching doc (the plan-time match counts, exact: segments are immutable), within PINOT_AMD_TOPK_SORT_MAX_BYTES
+  // for the array and as much for its sorted copy.
+  const int W = r->sel_words;
+  int64_t cap = 0;
+  if (r->sel_prune) {
+    for (auto& L : r->launches) cap += ((int64_t)L.grid + (int64_t)L.segs.size()) * std::max<int64_t>(r->sel_k, 1);
+  } else {
+    if (!Q.preds.empty()) {
+      if (int rc = probe_matched()) return rc;
+      for (int si = 0; si < n; ++si) cap += seg_matched[si];
+    } else {
+      cap = all_docs;
+    }
+    const int64_t maxb = env_i64("PINOT_AMD_TOPK_SORT_MAX_BYTES", (int64_t)4 << 30);
+    if ((double)cap * W * 8.0 > (double)maxb)
+      return fail(PINOT_AMD_EUNSUPPORTED, "selection of %lld rows sorts %lld matching docs' records (%.1f MB): above "
+                  "PINOT_AMD_TOPK_SORT_MAX_BYTES", (long long)r->sel_k, (long long)cap, (double)cap * W * 8.0 / 1e6);
+  }
+  cap = std::max<int64_t>(cap, 1);
+  r->sel_cap = cap;
+  if (int rc = r->tk_rec.alloc((size_t)cap * W * 8)) return rc;
+  if (int rc = r->tk_sorted.alloc((size_t)cap * W * 8)) return rc;
+  if (int rc = r->tk_scratch.alloc(sort_rows_scratch(cap))) return rc;
+  if (int rc = r->tk_ctr.alloc(16)) return rc;
+  if (int rc = r->tk_cnt.alloc((size_t)n * 4)) return rc;
+  if (int rc = r->tk_off.alloc((size_t)n * 8)) return rc;
+  // kept rows: each segment's first offset + limit, never more than the candidates
+  const int64_t rows = std::max<int64_t>(1, std::min<int64_t>(cap, (int64_t)n * std::max<int64_t>(r->sel_k, 1)));
+  if (int rc = r->tk_rseg.alloc((size_t)rows * 4)) return rc;
+  if (int rc = r->tk_rdoc.alloc((size_t)rows * 4)) return rc;
+  if (int rc = r->tk_vals.alloc((size_t)rows * (size_t)std::max(ncols, 1) * 8)) return rc;
+  for (auto& L : r->launches) {
+    L.q.tk_rec = (unsigned long long*)r->tk_rec.p;
+    L.q.tk_count = (unsigned long long*)r->tk_ctr.p;
+    L.q.tk_cap = cap;
+    L.q.tk_k = (int32_t)std::max<int64_t>(r->sel_k, 1);
+  }
+  return 0;
+}
+
 }  // namespace
 
 static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, int32_t n, void* stream,
@@ -4889,6 +5254,13 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
   std::vector<pinot_amd_segment*> segs(segs_in, segs_in + n);
   for (auto* s : segs)
     if (!s) return fail(PINOT_AMD_EINVAL, "execute: null segment");
+  // SelectionPlanNode: a query with output columns; it takes no aggregation and no GROUP BY
+  const bool sel = !filter_only && !qq->sel_cols.empty();
+  if (!filter_only && qq->sel_cols.empty() && !qq->sel_order.empty())
+    return fail(PINOT_AMD_EINVAL, "execute: selection ORDER BY without selection columns");
+  if (sel && (!qq->aggs.empty() || !qq->group_by.empty()))
+    return fail(PINOT_AMD_EINVAL, "execute: a selection query takes no aggregation and no GROUP BY");
+  if (sel && !qq->key_space.empty()) return fail(PINOT_AMD_EINVAL, "execute: a selection query takes no key space");
   const std::string plan_key = plan_identity(*qq, segs, filter_only);
   if (pinot_amd_result* hit = plan_cache_take(plan_key)) {  // a prepared plan of this identity: run it
     std::unique_ptr<pinot_amd_result> hold(hit);
@@ -4913,6 +5285,7 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
   b.n = n;
   b.stream = stream;
   b.filter_only = filter_only;
+  b.sel = sel;
   b.r = r;
   if (int rc = b.raw_keys()) return rc;
   clk.mark("raw_keys");
@@ -4935,6 +5308,8 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
   if (int rc = b.group_launches()) return rc;
   if (int rc = b.plan_launches()) return rc;
   if (int rc = b.alloc_buffers()) return rc;
+  if (sel)
+    if (int rc = b.selection_buffers()) return rc;
   clk.mark("jit_alloc");
   HIP_OK(hipEventCreate(&r->ev0));
   HIP_OK(hipEventCreate(&r->ev1));
@@ -5341,6 +5716,10 @@ static int verify_children(pinot_amd_result* r) {
 
 int pinot_amd_result_num_docs_matched(pinot_amd_result* r, int64_t* h_out) {
   if (!r || !h_out) return fail(PINOT_AMD_EINVAL, "num_docs_matched: bad arguments");
+  if (r->topk) {
+    *h_out = r->sel_matched;
+    return 0;
+  }
   std::vector<unsigned long long> c;
   if (int rc = read_counters(r, &c)) return rc;
   if (int rc = verify_partitioned(r, c)) return rc;
@@ -5363,8 +5742,11 @@ int pinot_amd_result_algorithmic_bytes(pinot_amd_result* r, double* h_bytes) {
   bool all_fused = !r->launches.empty();
   for (const auto& L : r->launches) all_fused &= L.fused;
   for (const auto& il : r->inv_leaves) b += il.alg_bytes + (all_fused ? 0.0 : il.bitset_bytes);
+  if (r->topk)  // the gathered columns of the rows fetched (the filter and ORDER BY columns: the launches below)
+    b += (double)r->sel_nrows * r->sel_key_bytes;
   for (size_t li = 0; li < r->launches.size(); ++li) {
     const Launch& L = r->launches[li];
+    if (r->topk && (r->sel_k == 0 || (r->sel_keys.empty() && L.batch >= r->sel_groups_run))) continue;  // not launched
     if (L.select) {  // filter columns of every doc, the vector written and read, the gathered columns
       const double m = (double)c[3 * li];
       b += L.filter_bytes + m * (16.0 + L.value_bpr);
@@ -5408,6 +5790,14 @@ const char* pinot_amd_result_packed_info(pinot_amd_result* r) {
 
 static std::string kernel_info_of(pinot_amd_result* r) {
   std::string info;
+  if (r->topk) {  // (" xN": the launches the last execution ran -- without ORDER BY it may stop early)
+    info = r->sel_prune ? "jit-topk" : "jit-topk-sort";
+    size_t ran = 0;
+    for (const auto& L : r->launches) ran += !(r->sel_keys.empty() && L.batch >= r->sel_groups_run);
+    if (r->sel_k == 0) ran = 0;
+    if (ran != 1) info += " x" + std::to_string(ran);
+    return info;
+  }
   switch (r->kind) {
     case PLAN_PARTITIONED: info = "jit-partitioned"; break;
     case PLAN_HASH: info = r->trim ? "jit-hash-trim" : "jit-hash"; break;
@@ -5632,6 +6022,7 @@ int pinot_amd_result_num_groups_limit_reached(pinot_amd_result* r, int32_t* h_ou
 
 int pinot_amd_result_num_groups(pinot_amd_result* r, int64_t* h_out) {
   if (!r || !h_out) return fail(PINOT_AMD_EINVAL, "num_groups: bad arguments");
+  if (r->topk) return fail(PINOT_AMD_EINVAL, "num_groups: a selection result has rows (pinot_amd_result_num_rows)");
   if (r->num_group_by == 0) {
     *h_out = 1;
     return 0;
@@ -5836,6 +6227,7 @@ static int server_trim(pinot_amd_result* r) {
 int pinot_amd_result_fetch(pinot_amd_result* r, int64_t cap, int64_t* h_keys, double* h_values, int64_t* h_values_i64,
                            int64_t* h_num_fetched) {
   if (!r || cap < 0 || !h_num_fetched) return fail(PINOT_AMD_EINVAL, "fetch: bad arguments");
+  if (r->topk) return fail(PINOT_AMD_EINVAL, "fetch: a selection result has rows (pinot_amd_result_fetch_rows)");
   if (int rc = no_throw("fetch", [&] { return compact_groups(r); })) return rc;
   const int na = (int)r->agg_type.size();
   const int nacc = cacc_stride(r);
@@ -5890,6 +6282,7 @@ int pinot_amd_result_fetch(pinot_amd_result* r, int64_t cap, int64_t* h_keys, do
 
 int pinot_amd_result_fetch_intermediate(pinot_amd_result* r, int64_t cap, double* h_pairs, int64_t* h_num_fetched) {
   if (!r || cap < 0 || !h_pairs || !h_num_fetched) return fail(PINOT_AMD_EINVAL, "fetch_intermediate: bad arguments");
+  if (r->topk) return fail(PINOT_AMD_EINVAL, "fetch_intermediate: a selection result has rows (pinot_amd_result_fetch_rows)");
   if (int rc = no_throw("fetch_intermediate", [&] { return compact_groups(r); })) return rc;
   if (r->ngroups > cap)
     return fail(PINOT_AMD_EOVERFLOW, "fetch_intermediate: %lld groups exceed capacity %lld", (long long)r->ngroups,
@@ -5934,6 +6327,49 @@ const char* pinot_amd_result_string_key(pinot_amd_result* r, int32_t j, int64_t 
   return m.vs[id].c_str();
 }
 
+int pinot_amd_result_selection_num_columns(pinot_amd_result* r, int32_t* h_out) {
+  if (!r || !h_out) return fail(PINOT_AMD_EINVAL, "selection_num_columns: bad arguments");
+  if (!r->topk) return fail(PINOT_AMD_EINVAL, "selection_num_columns: not a selection result");
+  *h_out = r->sel_nout;
+  return 0;
+}
+
+int pinot_amd_result_selection_column(pinot_amd_result* r, int32_t j, const char** h_name, int32_t* h_stored_type) {
+  if (!r || !r->topk) return fail(PINOT_AMD_EINVAL, "selection_column: not a selection result");
+  if (j < 0 || j >= r->sel_nout) return fail(PINOT_AMD_EINVAL, "selection_column: column %d out of range", j);
+  if (h_name) *h_name = r->sel_names[(size_t)j].c_str();
+  if (h_stored_type) *h_stored_type = r->sel_types[(size_t)j];
+  return 0;
+}
+
+int pinot_amd_result_num_rows(pinot_amd_result* r, int64_t* h_out) {
+  if (!r || !h_out) return fail(PINOT_AMD_EINVAL, "num_rows: bad arguments");
+  if (!r->topk) return fail(PINOT_AMD_EINVAL, "num_rows: not a selection result");
+  *h_out = r->sel_nrows;
+  return 0;
+}
+
+int pinot_amd_result_fetch_rows(pinot_amd_result* r, int64_t cap, int32_t* h_segment, int32_t* h_doc_id, int64_t* h_values,
+                                int64_t* h_num_fetched) {
+  if (!r || cap < 0 || !h_num_fetched) return fail(PINOT_AMD_EINVAL, "fetch_rows: bad arguments");
+  if (!r->topk) return fail(PINOT_AMD_EINVAL, "fetch_rows: not a selection result");
+  if (r->sel_nrows > cap)
+    return fail(PINOT_AMD_EOVERFLOW, "fetch_rows: %lld rows exceed capacity %lld", (long long)r->sel_nrows, (long long)cap);
+  const size_t nr = (size_t)r->sel_nrows;
+  if (h_segment && nr) memcpy(h_segment, r->row_seg.data(), nr * 4);
+  if (h_doc_id && nr) memcpy(h_doc_id, r->row_doc.data(), nr * 4);
+  if (h_values && nr) memcpy(h_values, r->row_vals.data(), nr * (size_t)r->sel_nout * 8);
+  *h_num_fetched = r->sel_nrows;
+  return 0;
+}
+
+const char* pinot_amd_result_selection_string(pinot_amd_result* r, int32_t j, int64_t id) {
+  if (!r || !r->topk || j < 0 || j >= r->sel_nout || (size_t)j >= r->row_strings.size()) return nullptr;
+  const std::vector<std::string>& t = r->row_strings[(size_t)j];
+  if (id < 0 || id >= (int64_t)t.size()) return nullptr;
+  return t[(size_t)id].c_str();
+}
+
 int pinot_amd_result_check_word(pinot_amd_result* r, void** h_d_word) {
   if (!r || !h_d_word) return fail(PINOT_AMD_EINVAL, "check_word: bad arguments");
   *h_d_word = (unsigned long long*)r->matched.p + 3 * r->launches.size() + 2;
@@ -5945,6 +6381,7 @@ int64_t pinot_amd_selfcheck_failures(void) { return (int64_t)g_selfcheck_failure
 int pinot_amd_result_accumulators(pinot_amd_result* r, int32_t* h_num_slots, int64_t* h_num_key_slots,
                                   void** h_slot_ptrs, int32_t* h_slot_ops) {
   if (!r || !h_num_slots || !h_num_key_slots) return fail(PINOT_AMD_EINVAL, "accumulators: bad arguments");
+  if (r->topk) return fail(PINOT_AMD_EUNSUPPORTED, "accumulators: a selection result has no accumulators");
   if (r->dc) return fail(PINOT_AMD_EUNSUPPORTED, "accumulators: a DISTINCTCOUNT result's value sets merge by union");
   if (r->kind == PLAN_HASH || r->merged)
     return fail(PINOT_AMD_EUNSUPPORTED, "accumulators: hash-table (and merged) results merge by value "
@@ -6012,6 +6449,7 @@ int pinot_amd_result_export_groups(pinot_amd_result* r, uint64_t* d_keys, uint64
                                    int32_t* h_key_words, int32_t* h_num_acc, int64_t* h_num_groups, void* stream) {
   if (!r || !h_key_words || !h_num_acc || !h_num_groups || cap < 0)
     return fail(PINOT_AMD_EINVAL, "export_groups: bad arguments");
+  if (r->topk) return fail(PINOT_AMD_EUNSUPPORTED, "export_groups: a selection result has no groups");
   if (r->dc) return fail(PINOT_AMD_EUNSUPPORTED, "export_groups: a DISTINCTCOUNT result's value sets merge by union");
   return no_throw("export_groups", [&]() -> int {
     if (r->num_group_by == 0 || r->q.nacc == 0)
@@ -6045,6 +6483,7 @@ int pinot_amd_result_export_groups(pinot_amd_result* r, uint64_t* d_keys, uint64
 int pinot_amd_result_merge_groups(pinot_amd_result* r, const uint64_t* d_keys, const uint64_t* d_acc, int64_t n,
                                   void* stream) {
   if (!r || n < 0 || (n > 0 && (!d_keys || !d_acc))) return fail(PINOT_AMD_EINVAL, "merge_groups: bad arguments");
+  if (r->topk) return fail(PINOT_AMD_EUNSUPPORTED, "merge_groups: a selection result has no groups");
   if (r->dc) return fail(PINOT_AMD_EUNSUPPORTED, "merge_groups: a DISTINCTCOUNT result's value sets merge by union");
   return no_throw("merge_groups", [&]() -> int {
     if (r->num_group_by == 0 || r->q.nacc == 0)

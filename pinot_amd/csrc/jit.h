@@ -183,7 +183,28 @@ struct JitPlan {
   struct OrdCol { int64_t stride, size, ostride; int flip; };
   std::vector<OrdCol> seg_ord;
   bool segpres = false;
+  // Selection top-K (SelectionOrderByOperator / SelectionOnlyOperator): the filter, then per matching doc a record
+  // (ORDER BY key, docId) comparable within its segment -- key field f reads slot topk_key[f].slot: a dictionary or
+  // sorted column's segment-local dictId, a raw INT / LONG with the sign bit flipped, a raw FLOAT / DOUBLE in
+  // Float.compare / Double.compare order; desc complements the field. Fields are 32 bits (dictId, INT, FLOAT) or 64
+  // (LONG, DOUBLE), at most 128 bits in all (jit_topk_words). The block keeps topk_rows records and a threshold
+  // in LDS: topk_prune appends only the docs that beat the threshold and reduces the buffer to its best
+  // DevQuery::tk_k records (bitonic sort) when it is short of room (a tile's 1024 docs at once while the buffer has room
+  // for all of them, else one doc per lane -- 256 -- at a time); without it every matching doc's record goes
+  // to the HBM array (the sort path). Flushed to DevQuery::tk_rec, tagged with the segment, when the block's tiles
+  // cross into another segment and at its end.
+  bool topk = false;
+  bool topk_prune = true;
+  int topk_rows = 0;  // records the LDS buffer holds: a power of two, >= 512
+  struct TopkField { int slot; int desc; };
+  std::vector<TopkField> topk_key;
 };
+// 64-bit words of a top-K record: the key fields, the docId (32 bits) and room for the segment tag (32 bits); 0 when
+// the key exceeds two words
+int jit_topk_words(const JitPlan& p);
+// LDS bytes of the top-K scan's buffer and counters (the filter's LDS tables follow it)
+size_t jit_topk_lds(const JitPlan& p);
+
 // record layout of a partitioned plan (fills val_off / rec_bytes from vals and val_bits)
 void jit_layout_records(JitPlan* p);
 // natural field width of a record value (no range known): 32 for INT / FLOAT, else 64

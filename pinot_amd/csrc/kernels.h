@@ -89,6 +89,12 @@ hipError_t launch_partition_offsets(const uint32_t* d_hist, int32_t nparts, int6
                                     int64_t* d_part_begin, hipStream_t st);
 hipError_t launch_allot_prefix(const uint32_t* d_hist, int32_t P, int64_t G, int mode, int64_t stride, double scale,
                                int64_t limit, int64_t* d_ptot, int64_t* d_out, hipStream_t st);
+hipError_t launch_selection_count(const uint64_t* sorted, int W, int64_t n, int64_t K, int32_t nsegs, uint32_t* cnt,
+                                  hipStream_t st);
+hipError_t launch_selection_cut(const uint64_t* sorted, int W, int64_t n, int64_t K, int32_t nsegs, const int64_t* off,
+                                int64_t total, uint32_t* out_seg, uint32_t* out_doc, hipStream_t st);
+hipError_t launch_selection_gather(const SelCol* cols, int32_t ncols, const uint32_t* row_seg, const uint32_t* row_doc,
+                                   int64_t nrows, int64_t* out, hipStream_t st);
 
 // derive.hip
 size_t derive_dictionary_scratch(int64_t n);

@@ -2613,4 +2613,123 @@ hipError_t launch_expand_jobs(const void* d_jobs, int32_t njobs, int64_t total_i
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// Selection (SelectionOrderByOperator.java:112-330): after the top-K scan's candidate records are sorted by
+// (segment, key words, docId) -- word W - 1 most significant, the segment in its high 32 bits, the docId in word
+// 0's low 32 -- each segment's first K rows are its result; their columns are then read by docId (the second-round
+// projection over the surviving rows only).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int64_t selection_seg_begin(const uint64_t* sorted, int W, int64_t n, uint32_t seg) {
+  int64_t lo = 0, hi = n;  // first row whose segment is >= seg
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if ((uint32_t)(sorted[mid * W + W - 1] >> 32) < seg) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// cnt[segment] = min(its candidate rows, K), written by the segment's last row (cnt zeroed before)
+__global__ void selection_count_kernel(const uint64_t* sorted, int W, int64_t n, int64_t K, int32_t nsegs, uint32_t* cnt) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t seg = (uint32_t)(sorted[i * W + W - 1] >> 32);
+    if (i + 1 < n && (uint32_t)(sorted[(i + 1) * W + W - 1] >> 32) == seg) continue;
+    if (seg >= (uint32_t)nsegs) continue;
+    const int64_t c = i + 1 - selection_seg_begin(sorted, W, n, seg);
+    cnt[seg] = (uint32_t)(c < K ? c : K);
+  }
+}
+
+// row `rank` (< K) of segment s to place off[s] + rank of the kept rows: its segment and docId
+__global__ void selection_cut_kernel(const uint64_t* sorted, int W, int64_t n, int64_t K, int32_t nsegs, const int64_t* off,
+                                     int64_t total, uint32_t* out_seg, uint32_t* out_doc) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t seg = (uint32_t)(sorted[i * W + W - 1] >> 32);
+    if (seg >= (uint32_t)nsegs) continue;
+    const int64_t rank = i - selection_seg_begin(sorted, W, n, seg);
+    if (rank >= K) continue;
+    const int64_t o = off[seg] + rank;
+    if (o >= total) continue;
+    out_seg[o] = seg;
+    out_doc[o] = (uint32_t)sorted[i * W];
+  }
+}
+
+// out[row * ncols + j] = column j of the row's doc in fetch's key encoding: int64, double bits (FLOAT widened), or
+// the segment's dictId for STRING. Runtime-typed random access: the fixed-bit dictId at the segment's width
+// (FixedBitIntReader.readInt), a sorted column by binary search in its first-docId array
+// (SortedIndexReaderImpl.getDictId), a raw big-endian value; numeric dictionaries looked up here.
+__global__ void selection_gather_kernel(const SelCol* cols, int32_t ncols, const uint32_t* row_seg, const uint32_t* row_doc,
+                                        int64_t nrows, int64_t* out) {
+  for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < nrows * ncols; x += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = x / ncols;
+    const int j = (int)(x - row * ncols);
+    const SelCol c = cols[(int64_t)row_seg[row] * ncols + j];
+    const int64_t d = (int64_t)row_doc[row];
+    const bool narrow = c.type == T_INT || c.type == T_FLOAT;
+    uint64_t bits;  // the value's native bits
+    if (c.enc == ENC_RAW) {
+      if (narrow) {
+        bits = bswap32(reinterpret_cast<const uint32_t*>(c.data)[d]);
+      } else {
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(c.data) + 2 * d;
+        bits = bswap64(w[0], w[1]);
+      }
+    } else {
+      int32_t id = 0;
+      if (c.enc == ENC_FIXED_BIT) {
+        if (c.bits > 0) {
+          const int64_t bit = d * (int64_t)c.bits;
+          const uint32_t* w = reinterpret_cast<const uint32_t*>(c.data + ((bit >> 5) << 2));
+          const uint64_t win = ((uint64_t)bswap32(w[0]) << 32) | (uint64_t)bswap32(w[1]);
+          id = (int32_t)((win << (bit & 31)) >> (64 - c.bits));
+        }
+      } else {
+        const int32_t* starts = reinterpret_cast<const int32_t*>(c.data);
+        int32_t lo = 0, hi = c.card - 1;
+        while (lo < hi) {
+          const int32_t mid = (lo + hi + 1) >> 1;
+          if ((int64_t)starts[mid] <= d) lo = mid; else hi = mid - 1;
+        }
+        id = lo;
+      }
+      if (c.type == T_STRING || !c.dict) {
+        out[x] = (int64_t)id;
+        continue;
+      }
+      if (id < 0 || id >= c.card) id = 0;
+      bits = narrow ? (uint64_t)reinterpret_cast<const uint32_t*>(c.dict)[id] : reinterpret_cast<const uint64_t*>(c.dict)[id];
+    }
+    int64_t v;
+    if (c.type == T_INT) v = (int64_t)(int32_t)(uint32_t)bits;
+    else if (c.type == T_FLOAT) v = __double_as_longlong((double)__uint_as_float((uint32_t)bits));
+    else v = (int64_t)bits;
+    out[x] = v;
+  }
+}
+
+static unsigned selection_grid(int64_t n) {
+  const int64_t g = (n + 255) / 256;
+  return (unsigned)(g < 1 ? 1 : g > 8192 ? 8192 : g);
+}
+hipError_t launch_selection_count(const uint64_t* sorted, int W, int64_t n, int64_t K, int32_t nsegs, uint32_t* cnt,
+                                  hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(selection_count_kernel, dim3(selection_grid(n)), dim3(256), 0, st, sorted, W, n, K, nsegs, cnt);
+  return hipGetLastError();
+}
+hipError_t launch_selection_cut(const uint64_t* sorted, int W, int64_t n, int64_t K, int32_t nsegs, const int64_t* off,
+                                int64_t total, uint32_t* out_seg, uint32_t* out_doc, hipStream_t st) {
+  if (n <= 0 || total <= 0) return hipSuccess;
+  hipLaunchKernelGGL(selection_cut_kernel, dim3(selection_grid(n)), dim3(256), 0, st, sorted, W, n, K, nsegs, off, total,
+                     out_seg, out_doc);
+  return hipGetLastError();
+}
+hipError_t launch_selection_gather(const SelCol* cols, int32_t ncols, const uint32_t* row_seg, const uint32_t* row_doc,
+                                   int64_t nrows, int64_t* out, hipStream_t st) {
+  if (nrows <= 0 || ncols <= 0) return hipSuccess;
+  hipLaunchKernelGGL(selection_gather_kernel, dim3(selection_grid(nrows * ncols)), dim3(256), 0, st, cols, ncols, row_seg,
+                     row_doc, nrows, out);
+  return hipGetLastError();
+}
+
 }  // namespace pamd

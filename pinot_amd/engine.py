@@ -11,6 +11,8 @@ Class names follow the reference so that tests and callers read like Pinot:
   executed in one batched device pass.
 * :class:`QueryResult` — ``AggregationGroupByResult`` / ``IntermediateResultsBlock``: per group the
   intermediate results of every aggregation (AVG as (sum, count)), mergeable across servers.
+* :class:`SelectionResult` — ``SelectionResultsBlock``: the server's offset + limit rows of a selection query
+  (``SelectionOnlyOperator`` / ``SelectionOrderByOperator`` -> ``SelectionOrderByCombineOperator``).
 
 Every computation goes through libpinot_amd.so; there is no CPU fallback.
 """
@@ -497,6 +499,100 @@ class QueryResult:
             pass
 
 
+class SelectionResult:
+    """Rows of one executed selection query (SELECT columns [ORDER BY ...] LIMIT n [OFFSET m]).
+
+    columns: the selected columns in select-list order (``*`` expanded); QueryContext.selection_columns gives the
+    server's schema order (ORDER BY columns first). The server keeps offset + limit rows; the broker applies the
+    offset. Ties of the ORDER BY come in ascending (segment index, docId)."""
+
+    def __init__(self, handle, qc: QueryContext, columns: List[str], types: List[str]):
+        self._h = handle
+        self.qc = qc
+        self.columns = columns
+        self._types = types
+
+    def execute_again(self, stream=None) -> None:
+        check(lib().pinot_amd_execute_again(self._h, _stream_handle(stream)), "execute_again")
+
+    def num_docs_matched(self) -> int:
+        """numDocsScanned: every matching doc with ORDER BY, the rows returned without."""
+        out = C.c_int64()
+        check(lib().pinot_amd_result_num_docs_matched(self._h, C.byref(out)), "num_docs_matched")
+        return out.value
+
+    def kernel_info(self) -> str:
+        """'jit-topk' (rows pruned in LDS) or 'jit-topk-sort', ' xN' for N launches run."""
+        return lib().pinot_amd_result_kernel_info(self._h).decode()
+
+    def packed_info(self) -> str:
+        return lib().pinot_amd_result_packed_info(self._h).decode()
+
+    def last_kernel_ms(self) -> float:
+        out = C.c_double()
+        check(lib().pinot_amd_result_last_kernel_ms(self._h, C.byref(out)), "last_kernel_ms")
+        return out.value
+
+    def algorithmic_bytes(self) -> float:
+        out = C.c_double()
+        check(lib().pinot_amd_result_algorithmic_bytes(self._h, C.byref(out)), "algorithmic_bytes")
+        return out.value
+
+    def plan_timing(self) -> Dict[str, float]:
+        txt = lib().pinot_amd_result_plan_timing(self._h).decode()
+        return {k: float(v) for k, v in (kv.split("=") for kv in txt.split(";") if kv)}
+
+    def fetch_arrays(self):
+        """(rows, segment index per row, docId per row, values [rows, columns] in fetch's key encoding)."""
+        L = lib()
+        n = C.c_int64()
+        check(L.pinot_amd_result_num_rows(self._h, C.byref(n)), "num_rows")
+        cap = max(n.value, 1)
+        nc = max(len(self.columns), 1)
+        seg = np.zeros(cap, dtype=np.int32)
+        doc = np.zeros(cap, dtype=np.int32)
+        vals = np.zeros(cap * nc, dtype=np.int64)
+        got = C.c_int64()
+        p32 = C.POINTER(C.c_int32)
+        check(L.pinot_amd_result_fetch_rows(self._h, cap, seg.ctypes.data_as(p32), doc.ctypes.data_as(p32),
+                                            vals.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(got)), "fetch_rows")
+        g = got.value
+        return g, seg[:g], doc[:g], vals[:g * nc].reshape(g, nc)
+
+    def origins(self) -> List[tuple]:
+        """(segment index in the batch, docId) of every row."""
+        _, seg, doc, _ = self.fetch_arrays()
+        return list(zip(seg.tolist(), doc.tolist()))
+
+    def rows(self) -> List[tuple]:
+        """The server's offset + limit rows, values in select-list order: STRINGs as str, FLOAT as Python floats of
+        the float32 value, DOUBLE as float, INT / LONG as int."""
+        L = lib()
+        g, _, _, vals = self.fetch_arrays()
+        cols = []
+        for j, t in enumerate(self._types):
+            col = np.ascontiguousarray(vals[:, j])
+            if t == STRING:
+                names = {int(i): L.pinot_amd_result_selection_string(self._h, j, int(i)).decode() for i in np.unique(col)}
+                cols.append([names[i] for i in col.tolist()])
+            elif t in (FLOAT, DOUBLE):
+                cols.append(col.view(np.float64).tolist())
+            else:
+                cols.append(col.tolist())
+        return list(zip(*cols)) if g else []
+
+    def destroy(self) -> None:
+        if self._h:
+            lib().pinot_amd_result_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
 class ServerQueryExecutor:
     """Compiles a QueryContext and runs it over a list of HBM-resident segments.
 
@@ -572,6 +668,10 @@ class ServerQueryExecutor:
         its global key space (dist.global_key_space: the union of every rank's dictionaries), so that
         every rank's dense group table indexes the same groups."""
         qc = parse_sql(query) if isinstance(query, str) else query
+        if qc.is_selection():
+            if key_space is not None:
+                raise _lib.PinotAmdError("a selection query takes no key_space (its rows merge by value at the broker)")
+            return self._execute_selection(qc, segments, stream)
         if any(a.func in VALUE_SET_FUNCS for a in qc.aggregations) and self.distinct_count == "native":
             if key_space is not None:
                 raise _lib.PinotAmdError("distinct_count='native' takes no key_space: results of several ranks merge "
@@ -594,6 +694,32 @@ class ServerQueryExecutor:
                                        [(i, self._execute(sq, segments, stream, key_space, server_trim=False))
                                         for i, sq in subs], server_trim=trim)
         return self._execute(qc, segments, stream, key_space)
+
+    def _execute_selection(self, qc: QueryContext, segments: Sequence[ImmutableSegment], stream=None) -> SelectionResult:
+        """SelectionPlanNode: the selected columns as the library's output columns, the ORDER BY, LIMIT and OFFSET."""
+        if not segments:
+            raise ValueError("no segments")
+        L = lib()
+        first = segments[0]
+        columns = qc.select_list(first)
+        if not columns:
+            raise ValueError("a selection query needs a column")
+        for c in columns + [c for c, _ in qc.order_by]:
+            if c not in first.columns:
+                raise _lib.PinotAmdError(f"unknown column {c!r} in segment {first.name}")
+        qh = self._compile(qc, segments)
+        try:
+            for c in columns:
+                check(L.pinot_amd_query_add_selection(qh, c.encode(), None), "add_selection")
+            for c, asc in qc.order_by:
+                check(L.pinot_amd_query_add_selection_order_by(qh, c.encode(), 1 if asc else 0), "add_selection_order_by")
+            check(L.pinot_amd_query_set_selection_limit(qh, qc.limit, qc.offset), "set_selection_limit")
+            arr = (C.c_void_p * len(segments))(*[s.handle.value for s in segments])
+            rh = C.c_void_p()
+            check(L.pinot_amd_execute(qh, arr, len(segments), _stream_handle(stream), C.byref(rh)), "execute")
+        finally:
+            L.pinot_amd_query_destroy(qh)
+        return SelectionResult(rh, qc, columns, [first.columns[c].stored_type for c in columns])
 
     @staticmethod
     def _set_key_space(qh, column: str, stored_type: str, values) -> None:

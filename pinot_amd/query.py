@@ -3,8 +3,8 @@
 Mirrors the pieces of pinot-core's request context that the hot path consumes
 (pinot-common/.../request/context/predicate/*Predicate.java, FilterContext.java,
 pinot-core/.../query/request/context/QueryContext.java): aggregation functions, GROUP BY
-expressions, the filter tree, ORDER BY / LIMIT for the final reduce, and the numGroupsLimit
-query option. Only the SQL this path executes is accepted (identifiers, numeric/string
+expressions, the filter tree, ORDER BY / LIMIT / OFFSET for the final reduce, and the numGroupsLimit
+query option. A query with neither aggregations nor GROUP BY is a selection query (SelectionPlanNode). Only the SQL this path executes is accepted (identifiers, numeric/string
 literals, comparisons, BETWEEN, [NOT] IN, AND/OR/NOT); anything else raises ValueError.
 """
 from __future__ import annotations
@@ -187,6 +187,41 @@ class QueryContext:
     # serverReturnFinalResult, sortAggregateLimitThreshold (CommonConstants: default 10000)
     server_return_final_result: bool = False
     sort_aggregate_limit_threshold: int = 10_000
+    offset: int = 0                     # LIMIT n OFFSET m / LIMIT m, n (the broker applies it; a server keeps offset + limit)
+
+    def is_selection(self) -> bool:
+        """SELECT columns [ORDER BY ...] LIMIT n: neither aggregations nor GROUP BY (SelectionPlanNode)."""
+        return not self.aggregations and not self.group_by
+
+    def select_list(self, segment=None) -> List[str]:
+        """The selected columns in select-list order, `*` expanded to every column of `segment` (an object with a
+        `columns` mapping) in String order (SelectionOperatorUtils.java:100-115), duplicates kept once."""
+        out = []
+        for c in self.select_columns:
+            if c == "*":
+                if segment is None:
+                    raise ValueError("SELECT * needs a segment to expand")
+                names = sorted(segment.columns, key=lambda n: n.encode("utf-16-be"))
+            else:
+                names = [c]
+            for n in names:
+                if n not in out:
+                    out.append(n)
+        return out
+
+    def selection_columns(self, segment=None) -> List[str]:
+        """The server's selection schema (SelectionOperatorUtils.extractExpressions, java:83-125): the ORDER BY
+        columns, deduplicated and in ORDER BY order, then the selected columns not among them in select-list order.
+        With LIMIT 0 the ORDER BY is ignored."""
+        out = []
+        if self.limit + self.offset > 0:
+            for c, _ in self.order_by:
+                if c not in out:
+                    out.append(c)
+        for c in self.select_list(segment):
+            if c not in out:
+                out.append(c)
+        return out
 
     def safe_trim(self) -> bool:
         """QueryContext._isUnsafeTrim is false: the ORDER BY expressions, as a set, are the GROUP BY ones (no
@@ -316,6 +351,9 @@ class _Parser:
                 elif self.peek()[0] == "id" and self.peek()[1].upper() not in ("FROM",):
                     alias = self.ident()   # implicit alias: sum(x) revenue
                 aggs.append(Aggregation(func, col, alias, expr, param))
+            elif tok == ("op", "*"):
+                self.i += 1
+                cols.append("*")
             else:
                 cols.append(self.ident())
             if self.peek() == ("op", ","):
@@ -343,13 +381,27 @@ class _Parser:
                 if self.peek() != ("op", ","):
                     break
                 self.i += 1
-        limit = DEFAULT_GROUP_BY_LIMIT
+        limit, offset = DEFAULT_GROUP_BY_LIMIT, 0
         if self.kw("LIMIT"):
             self.i += 1
-            limit = int(self.literal())
+            limit = self.count("LIMIT")
+            if self.peek() == ("op", ","):  # LIMIT offset, limit
+                self.i += 1
+                offset, limit = limit, self.count("LIMIT")
+            elif self.kw("OFFSET"):
+                self.i += 1
+                offset = self.count("OFFSET")
         if self.peek()[0] != "eof":
             raise ValueError(f"unexpected trailing token {self.peek()}")
-        return QueryContext(table, aggs, group_by, flt, order, limit, cols)
+        if "*" in cols and (aggs or group_by):
+            raise ValueError("SELECT * takes no aggregation and no GROUP BY")
+        return QueryContext(table, aggs, group_by, flt, order, limit, cols, offset=offset)
+
+    def count(self, what: str) -> int:
+        v = self.literal()
+        if not isinstance(v, int) or v < 0:
+            raise ValueError(f"{what} takes a non-negative integer, not {v!r}")
+        return v
 
     def percentile_arg(self, func, param):
         """PERCENTILE(c, 50) / PERCENTILE(c, 99.9) / PERCENTILE(c, '50'): the second argument, unless the
