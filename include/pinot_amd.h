@@ -214,6 +214,52 @@ int pinot_amd_query_add_predicate(pinot_amd_query* q, int32_t clause, const pino
  * floatToIntBits/doubleToLongBits). A raw column gets a derived dictionary twin staged on its segment
  * at the first such query (kept for later queries). */
 int pinot_amd_query_add_group_by(pinot_amd_query* q, const char* column);
+/* GROUP BY on a time bucket: one of three transform functions of a single-value INT / LONG column (raw,
+ * dictionary-encoded or sorted; the encoding may differ between the segments of a batch). All arithmetic is
+ * Java long; the key is a LONG: its values, their order and the group identity are those of a LONG column holding
+ * the transformed values.
+ *   DATETRUNC (DateTruncTransformFunction.java:132-142, DateTimeUtils.getTimestampField, UTC only):
+ *     out = out_unit.convert(roundFloor_trunc_unit(MILLISECONDS.convert(v, in_unit)), MILLISECONDS); roundFloor is
+ *     Joda's (a true floor: instants before 1970 round toward -inf), week floors to Monday 00:00, month / quarter /
+ *     year to the first instant of the civil month / quarter / year (ISOChronology: proleptic Gregorian, UTC).
+ *   TIMECONVERT (TimeConversionTransformFunction, JavaTimeUnitTransformer.java:37-41):
+ *     out = out_unit.convert(v, in_unit).
+ *   DATETIMECONVERT, EPOCH -> EPOCH without a bucketing time zone (EpochToEpochTransformer.java:44-46,
+ *     BaseDateTimeTransformer.java:208-243): ms = in_unit.toMillis(v * in_size) (the product wraps, toMillis
+ *     saturates); q = (ms / G) * G with G = gran_unit.toMillis(gran_size), the division truncating toward zero;
+ *     out = out_unit.convert(q, MILLISECONDS) / out_size.
+ * TimeUnit.convert is the JDK's: scaling down divides truncating toward zero, scaling up multiplies and saturates at
+ * Long.MIN_VALUE / Long.MAX_VALUE. */
+enum pinot_amd_time_unit { /* java.util.concurrent.TimeUnit, in its order */
+  PINOT_AMD_NANOSECONDS = 0, PINOT_AMD_MICROSECONDS = 1, PINOT_AMD_MILLISECONDS = 2, PINOT_AMD_SECONDS = 3,
+  PINOT_AMD_MINUTES = 4, PINOT_AMD_HOURS = 5, PINOT_AMD_DAYS = 6 };
+enum pinot_amd_trunc_unit { /* the units of DateTimeUtils.getTimestampField */
+  PINOT_AMD_TRUNC_MILLISECOND = 0, PINOT_AMD_TRUNC_SECOND = 1, PINOT_AMD_TRUNC_MINUTE = 2, PINOT_AMD_TRUNC_HOUR = 3,
+  PINOT_AMD_TRUNC_DAY = 4, PINOT_AMD_TRUNC_WEEK = 5, PINOT_AMD_TRUNC_MONTH = 6, PINOT_AMD_TRUNC_QUARTER = 7,
+  PINOT_AMD_TRUNC_YEAR = 8 };
+enum pinot_amd_key_transform { PINOT_AMD_KEY_DATETRUNC = 0, PINOT_AMD_KEY_TIMECONVERT = 1,
+                               PINOT_AMD_KEY_DATETIMECONVERT = 2 };
+typedef struct pinot_amd_key_transform_spec {
+  int32_t kind;        /* pinot_amd_key_transform */
+  int32_t trunc_unit;  /* pinot_amd_trunc_unit; DATETRUNC only */
+  int32_t in_unit;     /* pinot_amd_time_unit of the column's values */
+  int64_t in_size;     /* DATETIMECONVERT only: 'in_size:in_unit:EPOCH' */
+  int32_t out_unit;    /* pinot_amd_time_unit of the key */
+  int64_t out_size;    /* DATETIMECONVERT only: 'out_size:out_unit:EPOCH' */
+  int32_t gran_unit;   /* DATETIMECONVERT only: 'gran_size:gran_unit' */
+  int64_t gran_size;
+} pinot_amd_key_transform_spec;
+/* Appends a GROUP BY key in order with pinot_amd_query_add_group_by: its index (pinot_amd_query_add_order_by kind 0,
+ * the key columns of fetch / export_groups) is its position. A NULL argument, an enum out of range, a size <= 0 or a
+ * granularity below one millisecond (DATETIMECONVERT; the fields marked "only" are not read otherwise): EINVAL here.
+ * A STRING column: EINVAL, a FLOAT / DOUBLE column: EUNSUPPORTED, both from pinot_amd_execute. Time zones other than
+ * UTC, the WEEKS / MONTHS / YEARS outputs of CustomTimeUnitTransformer and SIMPLE_DATE_FORMAT / TIMESTAMP formats
+ * have no spec: callers refuse them. Every segment gets, at the first query that needs it, a dictionary-encoded
+ * twin of the transformed values (built on the device, kept staged per (column, spec), counted in
+ * pinot_amd_segment_device_bytes); the query then runs as a GROUP BY on that fixed-bit column. The spec is part of
+ * the query's identity: queries that differ only in it never share a prepared plan. */
+int pinot_amd_query_add_group_by_transform(pinot_amd_query* q, const char* column,
+                                           const pinot_amd_key_transform_spec* spec);
 /* Aggregation function (column NULL or "*" for COUNT(*)). Returns the aggregation index via out_index.
  * PINOT_AMD_AGG_DISTINCTCOUNT takes a column of any stored type, STRING included (EINVAL for NULL / "*").
  * Types above PINOT_AMD_AGG_DISTINCTCOUNT: EINVAL (pinot_amd_query_add_aggregation_param adds them). */
@@ -240,7 +286,9 @@ int pinot_amd_query_add_aggregation_expr(pinot_amd_query* q, int32_t agg_type, i
  * order; duplicates ignored): the union of the dictionaries of every server's segments, so that the
  * dense accumulator tables of all servers index groups identically and can be merged in place
  * (the broker merges by value: GroupByDataTableReducer.java:258). Must hold every dictionary value of
- * the segments executed (EINVAL otherwise). Without it the key space is the union over the batch. */
+ * the segments executed (EINVAL otherwise). Without it the key space is the union over the batch.
+ * EUNSUPPORTED when `column` is the column of a transformed key (pinot_amd_query_add_group_by_transform) and not a
+ * plain GROUP BY column of the query: a transformed key's space is always the union over the batch. */
 int pinot_amd_query_set_group_key_values(pinot_amd_query* q, const char* column, int32_t stored_type, int64_t n,
                                          const int64_t* h_values_i, const double* h_values_d,
                                          const char* const* h_values_s);

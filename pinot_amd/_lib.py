@@ -47,6 +47,13 @@ class PredicateSpec(C.Structure):
     ]
 
 
+class KeyTransformSpec(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32), ("trunc_unit", C.c_int32), ("in_unit", C.c_int32), ("in_size", C.c_int64),
+        ("out_unit", C.c_int32), ("out_size", C.c_int64), ("gran_unit", C.c_int32), ("gran_size", C.c_int64),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/pinot_amd.h
 _P = C.c_void_p
 _PP = C.POINTER(C.c_void_p)
@@ -77,6 +84,7 @@ SIGNATURES = {
     "pinot_amd_query_destroy": (C.c_int, [_P]),
     "pinot_amd_query_add_predicate": (C.c_int, [_P, C.c_int32, C.POINTER(PredicateSpec), C.c_int32]),
     "pinot_amd_query_add_group_by": (C.c_int, [_P, C.c_char_p]),
+    "pinot_amd_query_add_group_by_transform": (C.c_int, [_P, C.c_char_p, C.POINTER(KeyTransformSpec)]),
     "pinot_amd_query_add_aggregation": (C.c_int, [_P, C.c_int32, C.c_char_p, C.POINTER(C.c_int32)]),
     "pinot_amd_query_add_aggregation_param": (C.c_int, [_P, C.c_int32, C.c_char_p, C.c_double,
                                                         C.POINTER(C.c_int32)]),

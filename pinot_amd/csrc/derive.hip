@@ -11,12 +11,19 @@
 //   4. dict_ids_kernel:     per doc, the dictId (binary search in the distinct keys)
 //   5. dict_values_kernel:  distinct keys -> big-endian dictionary values (the staged dictionary format)
 // The fixed-bit packing reuses pack_dict_ids_kernel (kernels.hip).
+//
+// A transformed GROUP BY key (dateTrunc / timeConvert / dateTimeConvert of an INT / LONG column) gets its twin the
+// same way: step 1 becomes transform_keys_kernel, which writes the order-preserving key of f(value), and the
+// dictionary's values are LONG. A dictionary-encoded or sorted source derives over its dictionary's values (the
+// `ids` are then the old dictId -> twin dictId table) and maps the docs through that table
+// (remap_dict_ids_kernel / sorted_dict_ids_kernel).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "../../include/pinot_amd.h"
 #include "device_types.h"
 #include "kernels.h"
 
@@ -42,6 +49,158 @@ __global__ void order_keys_kernel(const uint8_t* be, int type, int64_t n, uint64
       k = type == T_LONG ? (u ^ (1ull << 63)) : java_double_order_dev(__longlong_as_double((long long)u));
     }
     keys[d] = k;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// GROUP BY key transforms (pinot_amd_query_add_group_by_transform): dateTrunc / timeConvert /
+// dateTimeConvert of an INT / LONG value, in Java long arithmetic. Products that Java lets wrap are computed
+// unsigned; every fixed divisor is a compile-time constant (a switch on the unit), only a granularity whose
+// size is not 1 divides by a run-time value.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int64_t wrap_mul(int64_t a, int64_t b) { return (int64_t)((uint64_t)a * (uint64_t)b); }
+__device__ __forceinline__ int64_t wrap_add(int64_t a, int64_t b) { return (int64_t)((uint64_t)a + (uint64_t)b); }
+
+// TimeUnit.convert(v, from) of unit `to` (TimeUnit ordinals, NANOSECONDS = 0 .. DAYS = 6). Scaling down is a
+// chain of truncating divisions by the steps between neighbouring units (truncation composes); scaling up
+// saturates (the JDK's bounds check equals mathematical saturation: no ratio is a power of two).
+__device__ __forceinline__ int64_t time_unit_convert(int64_t v, int from, int to) {
+  if (to > from) {
+    if (from <= 0 && to > 0) v /= 1000;
+    if (from <= 1 && to > 1) v /= 1000;
+    if (from <= 2 && to > 2) v /= 1000;
+    if (from <= 3 && to > 3) v /= 60;
+    if (from <= 4 && to > 4) v /= 60;
+    if (from <= 5 && to > 5) v /= 24;
+    return v;
+  }
+  if (to == from) return v;
+  int64_t ratio = 1;
+  if (to <= 0 && from > 0) ratio *= 1000;
+  if (to <= 1 && from > 1) ratio *= 1000;
+  if (to <= 2 && from > 2) ratio *= 1000;
+  if (to <= 3 && from > 3) ratio *= 60;
+  if (to <= 4 && from > 4) ratio *= 60;
+  if (to <= 5 && from > 5) ratio *= 24;
+  int64_t r;
+  if (__builtin_mul_overflow(v, ratio, &r)) r = v < 0 ? INT64_MIN : INT64_MAX;
+  return r;
+}
+
+// floor(a / C) * C for a constant C > 0 (Joda PreciseDateTimeField.roundFloor: toward -inf)
+template <int64_t C>
+__device__ __forceinline__ int64_t floor_to(int64_t a) {
+  int64_t q = a / C;
+  if (a % C < 0) --q;
+  return wrap_mul(q, C);
+}
+
+// days since 1970-01-01 of the first day of civil (y, m) and back, proleptic Gregorian (ISOChronology), 64-bit;
+// eras of 400 years = 146097 days starting on March 1
+__device__ __forceinline__ int64_t days_from_civil(int64_t y, int m) {
+  y -= m <= 2;
+  const int64_t era = (y >= 0 ? y : y - 399) / 400;
+  const int64_t yoe = y - era * 400;
+  const int64_t doy = (153 * (m > 2 ? m - 3 : m + 9) + 2) / 5;
+  const int64_t doe = yoe * 365 + yoe / 4 - yoe / 100 + doy;
+  return era * 146097 + doe - 719468;
+}
+__device__ __forceinline__ void civil_from_days(int64_t z, int64_t* y, int* m) {
+  z += 719468;
+  const int64_t era = (z >= 0 ? z : z - 146096) / 146097;
+  const int64_t doe = z - era * 146097;
+  const int64_t yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365;
+  const int64_t doy = doe - (365 * yoe + yoe / 4 - yoe / 100);
+  const int64_t mp = (5 * doy + 2) / 153;
+  *m = (int)(mp < 10 ? mp + 3 : mp - 9);
+  *y = yoe + era * 400 + (*m <= 2);
+}
+
+__device__ __forceinline__ int64_t date_trunc_floor(int64_t ms, int unit) {
+  constexpr int64_t kDay = 86400000;
+  switch (unit) {
+    case PINOT_AMD_TRUNC_SECOND: return floor_to<1000>(ms);
+    case PINOT_AMD_TRUNC_MINUTE: return floor_to<60000>(ms);
+    case PINOT_AMD_TRUNC_HOUR: return floor_to<3600000>(ms);
+    case PINOT_AMD_TRUNC_DAY: return floor_to<kDay>(ms);
+    case PINOT_AMD_TRUNC_WEEK: return wrap_add(floor_to<7 * kDay>(wrap_add(ms, 3 * kDay)), -3 * kDay);  // Monday
+    case PINOT_AMD_TRUNC_MONTH:
+    case PINOT_AMD_TRUNC_QUARTER:
+    case PINOT_AMD_TRUNC_YEAR: {
+      int64_t days = ms / kDay;
+      if (ms % kDay < 0) --days;
+      int64_t y;
+      int m;
+      civil_from_days(days, &y, &m);
+      if (unit == PINOT_AMD_TRUNC_YEAR) m = 1;
+      if (unit == PINOT_AMD_TRUNC_QUARTER) m = (m - 1) / 3 * 3 + 1;
+      return wrap_mul(days_from_civil(y, m), kDay);
+    }
+    default: return ms;  // millisecond
+  }
+}
+
+__device__ __forceinline__ int64_t key_transform_value(int64_t v, const DevKeyTransform& tf) {
+  constexpr int kMillis = PINOT_AMD_MILLISECONDS;
+  switch (tf.kind) {
+    case PINOT_AMD_KEY_DATETRUNC:
+      return time_unit_convert(date_trunc_floor(time_unit_convert(v, tf.in_unit, kMillis), tf.trunc_unit), kMillis,
+                               tf.out_unit);
+    case PINOT_AMD_KEY_TIMECONVERT: return time_unit_convert(v, tf.in_unit, tf.out_unit);
+    default: {  // DATETIMECONVERT
+      const int64_t ms = time_unit_convert(wrap_mul(v, tf.in_size), tf.in_unit, kMillis);
+      int64_t q;
+      switch (tf.gran_unit) {  // a granularity of size 1: constant divisors
+        case PINOT_AMD_MILLISECONDS: q = ms; break;
+        case PINOT_AMD_SECONDS: q = ms / 1000 * 1000; break;
+        case PINOT_AMD_MINUTES: q = ms / 60000 * 60000; break;
+        case PINOT_AMD_HOURS: q = ms / 3600000 * 3600000; break;
+        case PINOT_AMD_DAYS: q = ms / 86400000 * 86400000; break;
+        default: q = ms / tf.gran_ms * tf.gran_ms; break;
+      }
+      const int64_t o = time_unit_convert(q, kMillis, tf.out_unit);
+      return tf.out_size == 1 ? o : o / tf.out_size;
+    }
+  }
+}
+
+// step 1 of derive_dictionary for a transformed key: source values -> order-preserving keys of f(value).
+// src: DERIVE_SRC_BE (staged raw INT / LONG, byte-swapped loads) or DERIVE_SRC_LE64 (dictionary values)
+__global__ void transform_keys_kernel(const uint8_t* in, int type, int src, int64_t n, DevKeyTransform tf,
+                                      uint64_t* keys) {
+  for (int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; d < n; d += (int64_t)gridDim.x * blockDim.x) {
+    int64_t v;
+    if (src == DERIVE_SRC_LE64) {
+      v = reinterpret_cast<const int64_t*>(in)[d];
+    } else if (type == T_INT) {
+      v = (int64_t)(int32_t)__builtin_bswap32(reinterpret_cast<const uint32_t*>(in)[d]);
+    } else {
+      const uint2 w = reinterpret_cast<const uint2*>(in)[d];
+      v = (int64_t)(((uint64_t)__builtin_bswap32(w.x) << 32) | __builtin_bswap32(w.y));
+    }
+    keys[d] = (uint64_t)key_transform_value(v, tf) ^ (1ull << 63);
+  }
+}
+
+// a dictionary column's docs through the old dictId -> twin dictId table (card entries)
+__global__ void remap_dict_ids_kernel(int32_t* ids, int64_t n, const int32_t* map, int64_t card) {
+  for (int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; d < n; d += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t id = ids[d];
+    ids[d] = id >= 0 && id < card ? map[id] : 0;
+  }
+}
+
+// a sorted column's docs: the dictId is the last one whose first docId is <= the doc (starts ascending, starts[0]
+// = 0), then the same table
+__global__ void sorted_dict_ids_kernel(const int32_t* starts, int64_t card, int64_t n, const int32_t* map,
+                                       int32_t* ids) {
+  for (int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; d < n; d += (int64_t)gridDim.x * blockDim.x) {
+    int64_t lo = 0, hi = card - 1;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi + 1) >> 1;
+      if ((int64_t)starts[mid] <= d) lo = mid; else hi = mid - 1;
+    }
+    ids[d] = map[lo];
   }
 }
 
@@ -110,9 +269,12 @@ size_t derive_dictionary_scratch(int64_t n) {
   return (size_t)n * (8 + 8 + 4 + 4 + 8) + tmp + 256;
 }
 
-// -> *h_card distinct values; d_ids[n] the docs' dictIds; d_dict_be[card * value size] the dictionary
-hipError_t derive_dictionary(const uint8_t* d_be, int type, int64_t n, void* d_scratch, int32_t* d_ids,
-                             uint8_t* d_dict_be, int64_t* h_card, hipStream_t st) {
+// -> *h_card distinct values; d_ids[n] the items' dictIds; d_dict_be[card * value size] the dictionary.
+// tf == nullptr: the dictionary of the source values themselves (big-endian values of `type`). tf != nullptr: the
+// dictionary of f(value) of INT / LONG source values stored as `src` says; its values are LONG.
+hipError_t derive_dictionary(const uint8_t* d_src, int type, int src, const DevKeyTransform* tf, int64_t n,
+                             void* d_scratch, int32_t* d_ids, uint8_t* d_dict_be, int64_t* h_card, hipStream_t st) {
+  if (tf ? (type != T_INT && type != T_LONG) : src != DERIVE_SRC_BE) return hipErrorInvalidValue;
   if (n <= 0) {
     *h_card = 0;
     return hipSuccess;
@@ -129,7 +291,8 @@ hipError_t derive_dictionary(const uint8_t* d_be, int type, int64_t n, void* d_s
   if (e != hipSuccess) return e;
   e = rocprim::exclusive_scan(nullptr, scan_bytes, flags, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(order_keys_kernel, dim3(grid_of(n)), dim3(256), 0, st, d_be, type, n, keys);
+  if (tf) hipLaunchKernelGGL(transform_keys_kernel, dim3(grid_of(n)), dim3(256), 0, st, d_src, type, src, n, *tf, keys);
+  else hipLaunchKernelGGL(order_keys_kernel, dim3(grid_of(n)), dim3(256), 0, st, d_src, type, n, keys);
   e = rocprim::radix_sort_keys(tmp, sort_bytes, keys, sorted, (unsigned int)n, 0, 64, st);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(unique_flags_kernel, dim3(grid_of(n)), dim3(256), 0, st, sorted, n, flags);
@@ -143,8 +306,23 @@ hipError_t derive_dictionary(const uint8_t* d_be, int type, int64_t n, void* d_s
   const int64_t card = (int64_t)last[0] + last[1];
   hipLaunchKernelGGL(scatter_unique_kernel, dim3(grid_of(n)), dim3(256), 0, st, sorted, flags, pos, n, uniq);
   hipLaunchKernelGGL(dict_ids_kernel, dim3(grid_of(n)), dim3(256), 0, st, keys, n, uniq, card, d_ids);
-  hipLaunchKernelGGL(dict_values_kernel, dim3(grid_of(card)), dim3(256), 0, st, uniq, card, type, d_dict_be);
+  hipLaunchKernelGGL(dict_values_kernel, dim3(grid_of(card)), dim3(256), 0, st, uniq, card, tf ? (int)T_LONG : type,
+                     d_dict_be);
   *h_card = card;
+  return hipGetLastError();
+}
+
+hipError_t launch_remap_dict_ids(int32_t* ids, int64_t n, const int32_t* map, int64_t card, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(remap_dict_ids_kernel, dim3(grid_of(n)), dim3(256), 0, st, ids, n, map, card);
+  return hipGetLastError();
+}
+
+hipError_t launch_sorted_dict_ids(const int32_t* starts, int64_t card, int64_t n, const int32_t* map, int32_t* ids,
+                                  hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (card < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sorted_dict_ids_kernel, dim3(grid_of(n)), dim3(256), 0, st, starts, card, n, map, ids);
   return hipGetLastError();
 }
 

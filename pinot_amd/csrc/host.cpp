@@ -1236,6 +1236,11 @@ static uint64_t next_key_space_id() {
 struct pinot_amd_query {
   std::vector<PredSpec> preds;
   std::vector<std::string> group_by;
+  // transformed keys (pinot_amd_query_add_group_by_transform): the group_by entry of such a key is the name of its
+  // twin column, "<column>$<canonical spec>", so the spec is part of everything keyed by the GROUP BY list (plan
+  // identity, key caches, the value-set sub-queries' copies); twin name -> (source column, spec)
+  struct KeyTransform { std::string column; DevKeyTransform tf; };
+  std::map<std::string, KeyTransform> key_tf;
   // group-by column -> key space installed by the caller (the union of every server's dictionaries); shared,
   // immutable once installed (every plan of the query reads the same one, never a copy)
   std::map<std::string, std::shared_ptr<const MergedKeyColumn>> key_space;
@@ -1316,6 +1321,56 @@ int pinot_amd_query_add_group_by(pinot_amd_query* q, const char* column) {
   return 0;
 }
 
+int pinot_amd_query_add_group_by_transform(pinot_amd_query* q, const char* column,
+                                           const pinot_amd_key_transform_spec* spec) {
+  if (!q || !column || !*column || !spec) return fail(PINOT_AMD_EINVAL, "add_group_by_transform: bad arguments");
+  if (q->group_by.size() >= (size_t)kMaxGroupCols)
+    return fail(PINOT_AMD_EUNSUPPORTED, "add_group_by_transform: too many columns");
+  auto unit_ok = [](int32_t u) { return u >= PINOT_AMD_NANOSECONDS && u <= PINOT_AMD_DAYS; };
+  if (spec->kind < PINOT_AMD_KEY_DATETRUNC || spec->kind > PINOT_AMD_KEY_DATETIMECONVERT)
+    return fail(PINOT_AMD_EINVAL, "add_group_by_transform: bad kind %d", spec->kind);
+  if (!unit_ok(spec->in_unit) || !unit_ok(spec->out_unit))
+    return fail(PINOT_AMD_EINVAL, "add_group_by_transform: bad time unit %d / %d", spec->in_unit, spec->out_unit);
+  // the canonical spec: the fields the kind does not read are cleared, so equal transforms name one twin
+  DevKeyTransform tf{};
+  tf.kind = spec->kind;
+  tf.in_unit = spec->in_unit;
+  tf.out_unit = spec->out_unit;
+  tf.in_size = tf.out_size = tf.gran_ms = 1;
+  tf.gran_unit = -1;
+  if (spec->kind == PINOT_AMD_KEY_DATETRUNC) {
+    if (spec->trunc_unit < PINOT_AMD_TRUNC_MILLISECOND || spec->trunc_unit > PINOT_AMD_TRUNC_YEAR)
+      return fail(PINOT_AMD_EINVAL, "add_group_by_transform: bad dateTrunc unit %d", spec->trunc_unit);
+    tf.trunc_unit = spec->trunc_unit;
+  } else if (spec->kind == PINOT_AMD_KEY_DATETIMECONVERT) {
+    if (!unit_ok(spec->gran_unit))
+      return fail(PINOT_AMD_EINVAL, "add_group_by_transform: bad granularity unit %d", spec->gran_unit);
+    if (spec->in_size <= 0 || spec->out_size <= 0 || spec->gran_size <= 0)
+      return fail(PINOT_AMD_EINVAL, "add_group_by_transform: sizes must be positive (%lld, %lld, %lld)",
+                  (long long)spec->in_size, (long long)spec->out_size, (long long)spec->gran_size);
+    // DateTimeGranularitySpec.granularityToMillis = TimeUnit.toMillis(size): truncating below a millisecond
+    // (the reference then divides by zero), saturating above
+    static const int64_t per_ms[] = {1000000, 1000, 1, 1000, 60000, 3600000, 86400000};
+    int64_t g = 0;
+    if (spec->gran_unit < PINOT_AMD_MILLISECONDS) g = spec->gran_size / per_ms[spec->gran_unit];
+    else if (__builtin_mul_overflow(spec->gran_size, per_ms[spec->gran_unit], &g)) g = INT64_MAX;
+    if (g <= 0) return fail(PINOT_AMD_EINVAL, "add_group_by_transform: granularity below one millisecond");
+    tf.in_size = spec->in_size;
+    tf.out_size = spec->out_size;
+    tf.gran_ms = g;
+    if (spec->gran_size == 1) tf.gran_unit = spec->gran_unit;
+  }
+  char b[192];
+  static const char* const kind_name[] = {"datetrunc", "timeconvert", "datetimeconvert"};
+  snprintf(b, sizeof(b), "$%s(%d,%d,%lld,%d,%lld,%lld)", kind_name[tf.kind], tf.trunc_unit, tf.in_unit,
+           (long long)tf.in_size, tf.out_unit, (long long)tf.out_size, (long long)tf.gran_ms);
+  // ('2:HOURS' and '120:MINUTES' are one bucket: the twin is named by the granularity's milliseconds)
+  const std::string twin = std::string(column) + b;
+  q->key_tf[twin] = {column, tf};
+  q->group_by.push_back(twin);
+  return 0;
+}
+
 int pinot_amd_query_add_aggregation(pinot_amd_query* q, int32_t agg_type, const char* column, int32_t* out_index) {
   if (!q) return fail(PINOT_AMD_EINVAL, "add_aggregation: null query");
   if (agg_type < PINOT_AMD_AGG_COUNT || agg_type > PINOT_AMD_AGG_DISTINCTCOUNT)
@@ -1364,6 +1419,10 @@ int pinot_amd_query_set_group_key_values(pinot_amd_query* q, const char* column,
                                          const char* const* h_values_s) {
   if (!q || !column || n < 0 || stored_type < T_INT || stored_type > T_STRING)
     return fail(PINOT_AMD_EINVAL, "set_group_key_values: bad arguments");
+  const bool plain = std::find(q->group_by.begin(), q->group_by.end(), column) != q->group_by.end();
+  for (const auto& kt : q->key_tf)
+    if (kt.first == column || (!plain && kt.second.column == column))
+      return fail(PINOT_AMD_EUNSUPPORTED, "set_group_key_values: %s is a transformed GROUP BY key", column);
   MergedKeyColumn m;
   m.type = stored_type;
   m.id = next_key_space_id();
@@ -2295,6 +2354,36 @@ static int make_leaf_for_segment(pinot_amd_result* r, int si, pinot_amd_segment*
 // staged next to it ("<col>$dict": sorted distinct values in the same order as a Pinot dictionary +
 // a fixed-bit forward index of dictIds), so the device plan groups it exactly like a dictionary
 // column: same groups, same key values, same dense mixed-radix key space.
+// the last step of a derived twin: the docs' dictIds (device, nd entries) packed fixed-bit, the dictionary
+// (device, big-endian values of `type`, `card` of them) copied out, and both staged as column `name`
+static int stage_derived_twin(pinot_amd_segment* s, const std::string& name, int type, int64_t nd, const DevBuf& ids,
+                              const DevBuf& dict_be, int64_t card) {
+  const int vs = value_size(type);
+  const bool have = nd > 0 && card > 0;
+  card = std::max<int64_t>(card, 1);
+  int bits = 1;
+  while (card > 1 && (1ll << bits) < card) ++bits;  // PinotDataBitSet.getNumBitsPerValue(card - 1)
+  const size_t fb_bytes = (size_t)((nd * bits + 7) / 8);
+  DevBuf packed;
+  if (int rc = packed.alloc(fb_bytes + 8)) return rc;
+  HIP_OK(hipMemset(packed.p, 0, packed.n));
+  if (nd) HIP_OK(launch_pack_dict_ids((const int32_t*)ids.p, nd, bits, (uint8_t*)packed.p, nullptr));
+  std::vector<uint8_t> fb(fb_bytes + 8, 0), dict((size_t)card * vs, 0);
+  HIP_OK(hipMemcpy(fb.data(), packed.p, fb_bytes, hipMemcpyDeviceToHost));
+  if (have) HIP_OK(hipMemcpy(dict.data(), dict_be.p, dict.size(), hipMemcpyDeviceToHost));
+  pinot_amd_column_spec spec{};
+  spec.name = name.c_str();
+  spec.stored_type = type;
+  spec.encoding = ENC_FIXED_BIT;
+  spec.cardinality = (int32_t)card;
+  spec.bits_per_element = bits;
+  spec.h_fwd = fb.data();
+  spec.fwd_size = fb.size();
+  spec.h_dictionary = dict.data();
+  spec.dictionary_size = dict.size();
+  return pinot_amd_segment_add_column(s, &spec);
+}
+
 static int derive_raw_group_dictionary(pinot_amd_segment* s, const std::string& col, std::string* out_name) {
   *out_name = col + "$dict";
   if (s->cols.count(*out_name)) return 0;
@@ -2308,29 +2397,50 @@ static int derive_raw_group_dictionary(pinot_amd_segment* s, const std::string& 
   if (int rc = ids.alloc((size_t)std::max<int64_t>(nd, 1) * 4)) return rc;
   if (int rc = dict_be.alloc((size_t)std::max<int64_t>(nd, 1) * vs)) return rc;
   int64_t card = 0;
-  HIP_OK(derive_dictionary((const uint8_t*)c.fwd.p, c.type, nd, scratch.p, (int32_t*)ids.p, (uint8_t*)dict_be.p, &card,
-                           nullptr));
-  card = std::max<int64_t>(card, 1);
-  int bits = 1;
-  while (card > 1 && (1ll << bits) < card) ++bits;  // PinotDataBitSet.getNumBitsPerValue(card - 1)
-  const size_t fb_bytes = (size_t)((nd * bits + 7) / 8);
-  if (int rc = packed.alloc(fb_bytes + 8)) return rc;
-  HIP_OK(hipMemset(packed.p, 0, packed.n));
-  if (nd) HIP_OK(launch_pack_dict_ids((const int32_t*)ids.p, nd, bits, (uint8_t*)packed.p, nullptr));
-  std::vector<uint8_t> fb(fb_bytes + 8, 0), dict((size_t)card * vs, 0);
-  HIP_OK(hipMemcpy(fb.data(), packed.p, fb_bytes, hipMemcpyDeviceToHost));
-  if (nd) HIP_OK(hipMemcpy(dict.data(), dict_be.p, dict.size(), hipMemcpyDeviceToHost));
-  pinot_amd_column_spec spec{};
-  spec.name = out_name->c_str();
-  spec.stored_type = c.type;
-  spec.encoding = ENC_FIXED_BIT;
-  spec.cardinality = (int32_t)card;
-  spec.bits_per_element = bits;
-  spec.h_fwd = fb.data();
-  spec.fwd_size = fb.size();
-  spec.h_dictionary = dict.data();
-  spec.dictionary_size = dict.size();
-  return pinot_amd_segment_add_column(s, &spec);
+  HIP_OK(derive_dictionary((const uint8_t*)c.fwd.p, c.type, DERIVE_SRC_BE, nullptr, nd, scratch.p, (int32_t*)ids.p,
+                           (uint8_t*)dict_be.p, &card, nullptr));
+  return stage_derived_twin(s, *out_name, c.type, nd, ids, dict_be, card);
+}
+
+// GROUP BY on a transformed key (pinot_amd_query_add_group_by_transform): the segment gets, once per (column, spec),
+// a dictionary-encoded LONG twin of the transformed values, named `twin`. Routes by the source's encoding:
+//   raw INT / LONG   the staged values through derive_dictionary's transform step (n items)
+//   fixed-bit        the dictionary's values through it (card items: the ids are the old dictId -> twin dictId
+//                    table), then the docs' dictIds read, mapped through the table
+//   sorted           likewise, the docs' dictIds found by binary search in the first-docId array
+// The caller has checked the source column's type. Nothing is staged unless every step succeeded.
+static int derive_transform_twin(pinot_amd_segment* s, const std::string& col, const DevKeyTransform& tf,
+                                 const std::string& twin) {
+  if (s->cols.count(twin)) return 0;
+  const Column& c = *s->cols.at(col);
+  const int64_t nd = s->num_docs;
+  const bool raw = c.enc == ENC_RAW;
+  const int64_t items = raw ? nd : (int64_t)c.dict_i.size();
+  if (!raw && nd > 0 && items < 1) return fail(PINOT_AMD_EINVAL, "column %s: empty dictionary", col.c_str());
+  DevBuf scratch, ids, dict_be, src, doc_ids;
+  if (int rc = scratch.alloc(derive_dictionary_scratch(std::max<int64_t>(items, 1)))) return rc;
+  if (int rc = ids.alloc((size_t)std::max<int64_t>(items, 1) * 4)) return rc;
+  if (int rc = dict_be.alloc((size_t)std::max<int64_t>(items, 1) * 8)) return rc;
+  int64_t card = 0;
+  if (raw) {
+    HIP_OK(derive_dictionary((const uint8_t*)c.fwd.p, c.type, DERIVE_SRC_BE, &tf, nd, scratch.p, (int32_t*)ids.p,
+                             (uint8_t*)dict_be.p, &card, nullptr));
+    return stage_derived_twin(s, twin, T_LONG, nd, ids, dict_be, card);
+  }
+  if (nd > 0) {
+    if (int rc = src.alloc_copy(c.dict_i.data(), (size_t)items * 8, 64)) return rc;
+    HIP_OK(derive_dictionary((const uint8_t*)src.p, c.type, DERIVE_SRC_LE64, &tf, items, scratch.p, (int32_t*)ids.p,
+                             (uint8_t*)dict_be.p, &card, nullptr));
+    if (int rc = doc_ids.alloc((size_t)nd * 4)) return rc;
+    if (c.enc == ENC_SORTED) {
+      HIP_OK(launch_sorted_dict_ids((const int32_t*)c.fwd.p, items, nd, (const int32_t*)ids.p, (int32_t*)doc_ids.p,
+                                    nullptr));
+    } else {
+      HIP_OK(launch_read_dict_ids((const uint8_t*)c.fwd.p, c.bits, 0, nd, (int32_t*)doc_ids.p, nullptr));
+      HIP_OK(launch_remap_dict_ids((int32_t*)doc_ids.p, nd, (const int32_t*)ids.p, items, nullptr));
+    }
+  }
+  return stage_derived_twin(s, twin, T_LONG, nd, nd > 0 ? doc_ids : ids, dict_be, card);
 }
 
 static int build_merged_keys_uncached(const std::vector<pinot_amd_segment*>& segs, const std::string& col,
@@ -3267,7 +3377,7 @@ struct PlanBuild {
 };
 
 // the query the plan is built for: the filter alone (FilterPlanNode), or the query with raw GROUP BY columns
-// redirected to their derived dictionaries
+// redirected to their derived dictionaries and the twins of its transformed keys built where they are missing
 int PlanBuild::raw_keys() {
   if (filter_only) filter_q.preds = qq->preds;  // FilterPlanNode only: no projection, no aggregation
   Qp = filter_only ? &filter_q : qq;
@@ -3278,6 +3388,23 @@ int PlanBuild::raw_keys() {
   }
   for (size_t j = 0; j < Qp->group_by.size(); ++j) {
     const std::string g = Qp->group_by[j];  // a copy: the redirect below rewrites Qp->group_by[j]
+    auto kt = Qp->key_tf.find(g);
+    if (kt != Qp->key_tf.end()) {
+      // a transformed key: g already names its twin; every segment gets one, whatever the source's encoding
+      // (checked over the whole batch first: a refusal stages nothing)
+      const std::string& col = kt->second.column;
+      for (auto* s : segs) {
+        auto it = s->cols.find(col);
+        if (it == s->cols.end()) return fail(PINOT_AMD_EINVAL, "segment %s has no column %s", s->name.c_str(), col.c_str());
+        if (it->second->type == T_STRING)
+          return fail(PINOT_AMD_EINVAL, "GROUP BY transform of STRING column %s", col.c_str());
+        if (is_float(it->second->type))
+          return fail(PINOT_AMD_EUNSUPPORTED, "GROUP BY transform of FLOAT / DOUBLE column %s", col.c_str());
+      }
+      for (auto* s : segs)
+        if (int rc = derive_transform_twin(s, col, kt->second.tf, g)) return rc;
+      continue;
+    }
     int nraw = 0;
     for (auto* s : segs) {
       auto it = s->cols.find(g);

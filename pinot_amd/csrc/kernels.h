@@ -97,9 +97,25 @@ hipError_t launch_selection_gather(const SelCol* cols, int32_t ncols, const uint
                                    int64_t nrows, int64_t* out, hipStream_t st);
 
 // derive.hip
+// A GROUP BY key transform as the transform kernel takes it (by value): pinot_amd_key_transform_spec after
+// validation, the granularity already in milliseconds. Units are java.util.concurrent.TimeUnit ordinals.
+struct DevKeyTransform {
+  int32_t kind;        // pinot_amd_key_transform
+  int32_t trunc_unit;  // pinot_amd_trunc_unit (DATETRUNC)
+  int32_t in_unit, out_unit;
+  int32_t gran_unit;   // DATETIMECONVERT: the granularity's unit when its size is 1 (a constant divisor), else -1
+  int64_t in_size, out_size;
+  int64_t gran_ms;     // DATETIMECONVERT: G.toMillis(g) > 0
+};
+// how derive_dictionary's source values are stored
+enum DeriveSource { DERIVE_SRC_BE = 0 /* staged raw column: big-endian values of `type` */,
+                    DERIVE_SRC_LE64 = 1 /* int64 in host order (a dictionary's values) */ };
 size_t derive_dictionary_scratch(int64_t n);
-hipError_t derive_dictionary(const uint8_t* d_be, int type, int64_t n, void* d_scratch, int32_t* d_ids,
-                             uint8_t* d_dict_be, int64_t* h_card, hipStream_t st);
+hipError_t derive_dictionary(const uint8_t* d_src, int type, int src, const DevKeyTransform* tf, int64_t n,
+                             void* d_scratch, int32_t* d_ids, uint8_t* d_dict_be, int64_t* h_card, hipStream_t st);
+hipError_t launch_remap_dict_ids(int32_t* ids, int64_t n, const int32_t* map, int64_t card, hipStream_t st);
+hipError_t launch_sorted_dict_ids(const int32_t* starts, int64_t card, int64_t n, const int32_t* map, int32_t* ids,
+                                  hipStream_t st);
 size_t sort_rows_scratch(int64_t n);
 hipError_t sort_rows_by_key(const uint64_t* keys, int nwk, const int* word_bits, const uint64_t* acc, int nacc, int64_t n,
                             void* scratch, uint64_t* keys_out, uint64_t* acc_out, hipStream_t st);

@@ -397,11 +397,22 @@ def local_key_values(segments, column: str, executor=None) -> list:
     return list(vals.values())
 
 
+def _refuse_key_transforms(group_by: Sequence[str]) -> None:
+    """A transformed GROUP BY key (dateTrunc / timeConvert / dateTimeConvert) has no installable key space
+    (pinot_amd_query_set_group_key_values: EUNSUPPORTED), so ranks cannot agree on one: not a multi-GPU query."""
+    from .query import key_transform
+    for g in group_by:
+        if key_transform(g) is not None:
+            raise ValueError(f"GROUP BY {g}: a transformed key has no global key space (multi-GPU execution of "
+                             "time-bucket keys is not supported)")
+
+
 def key_columns(qc) -> list:
     """Columns whose key space must be global for a cross-rank merge: the GROUP BY columns, and the
     DISTINCTCOUNT / PERCENTILE / DISTINCTSUM / DISTINCTAVG columns (their device queries group by them too)."""
     from .query import VALUE_SET_FUNCS
     cols = list(qc.group_by)
+    _refuse_key_transforms(cols)
     for a in qc.aggregations:
         if a.func in VALUE_SET_FUNCS and a.column not in cols:
             cols.append(a.column)
@@ -473,6 +484,7 @@ def global_key_space(segments, group_by: Sequence[str], group=None, executor=Non
     occurrence in rank order."""
     import torch.distributed as dist
     from .query import distinct_value
+    _refuse_key_transforms(group_by)
     mine = {g: local_key_values(segments, g, executor) for g in group_by}
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     gathered = {}

@@ -26,9 +26,10 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import ColumnSpec, PredicateSpec, check, lib
-from .query import (VALUE_SET_FUNCS, DistinctSize, FinalValue, JavaDouble, QueryContext, fold_distinct_count,
-                    hists_from_csr, parse_sql, reduce_rows, server_table, sets_from_csr, split_distinct_count)
+from ._lib import ColumnSpec, KeyTransformSpec, PredicateSpec, check, lib
+from .query import (KEY_TRANSFORMS, TIME_UNITS, TRUNC_UNITS, VALUE_SET_FUNCS, DistinctSize, FinalValue, JavaDouble,
+                    QueryContext, fold_distinct_count, hists_from_csr, key_transform, parse_sql, reduce_rows,
+                    server_table, sets_from_csr, split_distinct_count)
 from .segment import ColumnBuffers, SegmentBuffers, DOUBLE, FLOAT, INT, LONG, STRING
 
 TYPE_CODE = {INT: 0, LONG: 1, FLOAT: 2, DOUBLE: 3, STRING: 4}
@@ -37,6 +38,17 @@ PRED_CODE = {"EQ": 0, "NOT_EQ": 1, "IN": 2, "NOT_IN": 3, "RANGE": 4}
 AGG_CODE = {"COUNT": 0, "SUM": 1, "MIN": 2, "MAX": 3, "SUMLONG": 4, "AVG": 5, "MINMAXRANGE": 6,
             "DISTINCTCOUNT": 7, "PERCENTILE": 8, "DISTINCTSUM": 9, "DISTINCTAVG": 10}
 EXPR_CODE = {"MUL": 1, "SUB": 2, "ADD": 3}
+
+
+def key_transform_spec(kt) -> KeyTransformSpec:
+    """pinot_amd_key_transform_spec of a query.KeyTransform."""
+    s = KeyTransformSpec()
+    s.kind = KEY_TRANSFORMS.index(kt.kind)
+    s.trunc_unit = TRUNC_UNITS.index(kt.trunc_unit) if kt.trunc_unit else 0
+    s.in_unit, s.in_size = TIME_UNITS.index(kt.in_unit), kt.in_size
+    s.out_unit, s.out_size = TIME_UNITS.index(kt.out_unit), kt.out_size
+    s.gran_unit, s.gran_size = (TIME_UNITS.index(kt.gran_unit) if kt.gran_unit else 0), kt.gran_size
+    return s
 
 
 def _stream_handle(stream) -> Optional[int]:
@@ -753,6 +765,15 @@ class ServerQueryExecutor:
                     spec = _predicate_spec(pred, col, self.use_inverted_index, keep)
                     check(L.pinot_amd_query_add_predicate(qh, ci, C.byref(spec), 1 if neg else 0), "add_predicate")
             for g in qc.group_by:
+                kt = key_transform(g)
+                if kt is not None:  # a time-bucket key: bound by its spec, its key space the union over the batch
+                    if key_space is not None:
+                        raise _lib.PinotAmdError(f"GROUP BY {g} takes no key_space (a transformed key's space is "
+                                                 "the union over the batch)")
+                    spec = key_transform_spec(kt)
+                    check(L.pinot_amd_query_add_group_by_transform(qh, kt.column.encode(), C.byref(spec)),
+                          f"add_group_by_transform({g})")
+                    continue
                 check(L.pinot_amd_query_add_group_by(qh, g.encode()), "add_group_by")
                 if key_space is not None and g in key_space:
                     self._set_key_space(qh, g, first.columns[g].stored_type, key_space[g])
@@ -816,7 +837,7 @@ class ServerQueryExecutor:
             check(L.pinot_amd_execute(qh, arr, len(segments), _stream_handle(stream), C.byref(rh)), "execute")
         finally:
             L.pinot_amd_query_destroy(qh)
-        key_types = [first.columns[g].stored_type for g in qc.group_by]
+        key_types = [LONG if key_transform(g) is not None else first.columns[g].stored_type for g in qc.group_by]
         res = QueryResult(rh, qc, agg_slots, key_types)
         res._native_aggs = native
         return res

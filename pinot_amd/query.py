@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import collections
 import dataclasses
+import functools
 import math
 import re
 import struct
@@ -170,6 +171,129 @@ class Aggregation:
         return (self.expr[1], self.expr[2]) if self.expr else (self.column,)
 
 
+TIME_UNITS = ("NANOSECONDS", "MICROSECONDS", "MILLISECONDS", "SECONDS", "MINUTES", "HOURS", "DAYS")  # TimeUnit
+TRUNC_UNITS = ("millisecond", "second", "minute", "hour", "day", "week", "month", "quarter", "year")
+KEY_TRANSFORMS = ("datetrunc", "timeconvert", "datetimeconvert")  # canonical names: lower case, no underscores
+
+
+@dataclasses.dataclass(frozen=True)
+class KeyTransform:
+    """A GROUP BY key that is a time-bucket function of one INT / LONG column (pinot_amd_key_transform_spec):
+    dateTrunc(unit, col [, inputUnit [, tz [, outputUnit]]]), timeConvert(col, inputUnit, outputUnit) or
+    dateTimeConvert(col, 'a:U:EPOCH', 'b:W:EPOCH', 'g:G'). Units are TimeUnit names; the key is a LONG."""
+    kind: str                 # datetrunc | timeconvert | datetimeconvert
+    column: str
+    in_unit: str = "MILLISECONDS"
+    out_unit: str = "MILLISECONDS"
+    trunc_unit: Optional[str] = None   # datetrunc
+    in_size: int = 1                   # datetimeconvert
+    out_size: int = 1
+    gran_unit: Optional[str] = None
+    gran_size: int = 1
+
+    @property
+    def text(self) -> str:
+        """The canonical text: what QueryContext.group_by holds and SELECT / ORDER BY items are matched by."""
+        if self.kind == "datetrunc":
+            return f"datetrunc('{self.trunc_unit}',{self.column},'{self.in_unit}','UTC','{self.out_unit}')"
+        if self.kind == "timeconvert":
+            return f"timeconvert({self.column},'{self.in_unit}','{self.out_unit}')"
+        return (f"datetimeconvert({self.column},'{self.in_size}:{self.in_unit}:EPOCH',"
+                f"'{self.out_size}:{self.out_unit}:EPOCH','{self.gran_size}:{self.gran_unit}')")
+
+
+def _time_unit(s, what: str, func: str) -> str:
+    u = str(s).upper()
+    if u in ("WEEKS", "MONTHS", "YEARS"):  # CustomTimeUnitTransformer / DateTimeFormatUnitSpec's custom units
+        raise ValueError(f"{func}: {what} {u} is not supported (only TimeUnit NANOSECONDS .. DAYS)")
+    if u not in TIME_UNITS:
+        raise ValueError(f"{func}: bad {what} {s!r}")
+    return u
+
+
+def _epoch_format(s, what: str) -> Tuple[int, str]:
+    """'size:UNIT:EPOCH' (DateTimeFormatSpec's colon form) -> (size, unit)."""
+    parts = str(s).split(":")
+    fmt = parts[2].upper() if len(parts) >= 3 else ""
+    if "|" in str(s) or fmt in ("SIMPLE_DATE_FORMAT", "TIMESTAMP") or len(parts) > 3:
+        raise ValueError(f"dateTimeConvert: {what} {s!r} is not supported (only 'size:UNIT:EPOCH')")
+    if len(parts) != 3 or fmt != "EPOCH":
+        raise ValueError(f"dateTimeConvert: bad {what} {s!r}")
+    return _positive_size(parts[0], what), _time_unit(parts[1], what + " unit", "dateTimeConvert")
+
+
+def _positive_size(s, what: str) -> int:
+    try:
+        n = int(s)
+    except ValueError:
+        raise ValueError(f"dateTimeConvert: bad {what} size {s!r}") from None
+    if n <= 0:
+        raise ValueError(f"dateTimeConvert: {what} size must be positive, not {n}")
+    return n
+
+
+def make_key_transform(func: str, args: Sequence[Tuple[str, object]]) -> KeyTransform:
+    """The KeyTransform of a call: func is the canonical name, args are ('id' | 'str' | 'num', value) tokens.
+    Optional arguments take Pinot's defaults; unsupported forms raise ValueError naming the form."""
+    def strs(items, what):
+        for k, v in items:
+            if k != "str":
+                raise ValueError(f"{what}: expected a string literal, not {v!r}")
+        return [v for _, v in items]
+
+    if func == "datetrunc":   # DateTruncTransformFunction.init
+        if not 2 <= len(args) <= 5:
+            raise ValueError("dateTrunc takes two to five arguments")
+        if args[0][0] not in ("str", "id") or args[1][0] != "id":
+            raise ValueError("dateTrunc(unit, column, ...): the unit is a literal, the value a column")
+        unit = str(args[0][1]).lower()
+        if unit not in TRUNC_UNITS:
+            raise ValueError(f"dateTrunc: bad unit {args[0][1]!r}")
+        rest = strs(args[2:], "dateTrunc")
+        in_unit = _time_unit(rest[0], "input unit", "dateTrunc") if rest else "MILLISECONDS"
+        if len(rest) >= 2 and rest[1].upper() != "UTC":
+            raise ValueError(f"dateTrunc: time zone {rest[1]!r} is not supported (only UTC)")
+        out_unit = _time_unit(rest[2], "output unit", "dateTrunc") if len(rest) >= 3 else in_unit
+        return KeyTransform("datetrunc", args[1][1], in_unit, out_unit, trunc_unit=unit)
+    if func == "timeconvert":  # TimeConversionTransformFunction.init
+        if len(args) != 3 or args[0][0] != "id":
+            raise ValueError("timeConvert(column, inputUnit, outputUnit) takes a column and two units")
+        rest = strs(args[1:], "timeConvert")
+        return KeyTransform("timeconvert", args[0][1], _time_unit(rest[0], "input unit", "timeConvert"),
+                            _time_unit(rest[1], "output unit", "timeConvert"))
+    if func == "datetimeconvert":  # DateTimeConversionTransformFunction.init
+        if len(args) == 5:
+            raise ValueError("dateTimeConvert: a bucketing time zone argument is not supported")
+        if len(args) != 4 or args[0][0] != "id":
+            raise ValueError("dateTimeConvert(column, inputFormat, outputFormat, granularity) takes four arguments")
+        rest = strs(args[1:], "dateTimeConvert")
+        in_size, in_unit = _epoch_format(rest[0], "input format")
+        out_size, out_unit = _epoch_format(rest[1], "output format")
+        g = rest[2].split(":")
+        if len(g) != 2:
+            raise ValueError(f"dateTimeConvert: bad granularity {rest[2]!r}")
+        gran_unit = _time_unit(g[1], "granularity unit", "dateTimeConvert")
+        return KeyTransform("datetimeconvert", args[0][1], in_unit, out_unit, in_size=in_size, out_size=out_size,
+                            gran_unit=gran_unit, gran_size=_positive_size(g[0], "granularity"))
+    raise ValueError(f"unknown key transform {func}")
+
+
+def key_transform(text: str) -> Optional[KeyTransform]:
+    """The parsed transform of a GROUP BY item's text (canonical or as written), None for a plain column."""
+    return _key_transform(text) if "(" in text else None
+
+
+@functools.lru_cache(maxsize=256)
+def _key_transform(text: str) -> Optional[KeyTransform]:
+    p = _Parser(text)
+    if not p.transform_ahead():
+        return None
+    kt = p.transform_call()
+    if p.peek()[0] != "eof":
+        raise ValueError(f"unexpected trailing token {p.peek()}")
+    return kt
+
+
 @dataclasses.dataclass
 class QueryContext:
     table: str
@@ -321,6 +445,34 @@ class _Parser:
         self.i += 1
         return tok[1]
 
+    def transform_ahead(self) -> bool:
+        """At dateTrunc( / timeConvert( / dateTimeConvert( in any letter case, underscores ignored (Pinot
+        canonicalises function names the same way)."""
+        tok = self.peek()
+        return (tok[0] == "id" and tok[1].replace("_", "").lower() in KEY_TRANSFORMS
+                and self.peek(1) == ("op", "("))
+
+    def transform_call(self) -> KeyTransform:
+        func = self.ident().replace("_", "").lower()
+        self.eat_op("(")
+        args = []
+        while True:
+            tok = self.peek()
+            if tok[0] not in ("id", "str", "num"):
+                raise ValueError(f"{func}: expected a column or a literal at {tok}")
+            self.i += 1
+            args.append(tok)
+            if self.peek() != ("op", ","):
+                break
+            self.i += 1
+        self.eat_op(")")
+        return make_key_transform(func, args)
+
+    def key_item(self) -> str:
+        """A GROUP BY / SELECT / ORDER BY item that is not an aggregation: a column, or a key transform as its
+        canonical text."""
+        return self.transform_call().text if self.transform_ahead() else self.ident()
+
     # -- grammar --
     def query(self) -> QueryContext:
         self.eat_kw("SELECT")
@@ -355,7 +507,7 @@ class _Parser:
                 self.i += 1
                 cols.append("*")
             else:
-                cols.append(self.ident())
+                cols.append(self.key_item())
             if self.peek() == ("op", ","):
                 self.i += 1
                 continue
@@ -369,10 +521,10 @@ class _Parser:
         group_by = []
         if self.kw("GROUP", "BY"):
             self.i += 2
-            group_by.append(self.ident())
+            group_by.append(self.key_item())
             while self.peek() == ("op", ","):
                 self.i += 1
-                group_by.append(self.ident())
+                group_by.append(self.key_item())
         order = []
         if self.kw("ORDER", "BY"):
             self.i += 2
@@ -395,6 +547,11 @@ class _Parser:
             raise ValueError(f"unexpected trailing token {self.peek()}")
         if "*" in cols and (aggs or group_by):
             raise ValueError("SELECT * takes no aggregation and no GROUP BY")
+        for c in cols + [e for e, _ in order]:
+            if "(" in c and key_transform(c) is not None and c not in group_by:
+                if not aggs and not group_by:
+                    raise ValueError("a key transform in a selection query is not supported (only as a GROUP BY key)")
+                raise ValueError(f"{c} is not a GROUP BY key of the query")
         return QueryContext(table, aggs, group_by, flt, order, limit, cols, offset=offset)
 
     def count(self, what: str) -> int:
@@ -446,7 +603,7 @@ class _Parser:
             self.eat_op(")")
             expr = agg_text(func, col, param)
         else:
-            expr = self.ident()
+            expr = self.key_item()
         asc = True
         if self.kw("DESC"):
             self.i += 1
