@@ -282,6 +282,28 @@ enum pinot_amd_expr_op { PINOT_AMD_EXPR_COLUMN = 0, PINOT_AMD_EXPR_MUL = 1, PINO
                          PINOT_AMD_EXPR_ADD = 3 };
 int pinot_amd_query_add_aggregation_expr(pinot_amd_query* q, int32_t agg_type, int32_t expr_op, const char* column_a,
                                          const char* column_b, int32_t* out_index);
+/* Filtered aggregation, AGG(x) FILTER (WHERE f): one leaf of the CNF of the filter of aggregation `agg_index` (what
+ * pinot_amd_query_add_aggregation* returned); clauses and leaves as in pinot_amd_query_add_predicate, the clauses
+ * numbered from 0 per aggregation. The aggregation takes exactly the docs matching the main filter AND f
+ * (AggregationFunctionUtils.buildFilteredAggregationInfos, java:386-477; an aggregation without a filter takes the
+ * main filter's docs). Replaces FilteredGroupByOperator / FilteredAggregationOperator: aggregations with equal
+ * filters share one "lane" of the one scan, which evaluates every lane's clauses beside the main filter's. GROUP BY:
+ * the groups are the main filter's, also when every aggregation is filtered (java:462-474); a group without a doc
+ * in some lane has that function's empty value there (COUNT 0, SUM 0, MIN +inf, MAX / AVG / MINMAXRANGE -inf), and
+ * pinot_amd_result_num_docs_matched stays the docs matching the main filter.
+ * Limits: the main filter's and every lane's leaves together at most 16, their clauses at most 16, the accumulators
+ * (a filtered COUNT and the count of a filtered AVG are accumulators of their lane) at most 16: EUNSUPPORTED here
+ * where it is knowable, else at pinot_amd_execute. pinot_amd_execute also returns EUNSUPPORTED for a filtered query
+ * where a segment may reach numGroupsLimit (the reference admits groups across lanes in a HashMap's iteration
+ * order there: unspecified), with a segment-level trim (pinot_amd_query_set_server_options /
+ * pinot_amd_query_set_segment_trim) and with DISTINCTCOUNT / PERCENTILE / DISTINCTSUM / DISTINCTAVG in the query;
+ * EINVAL for a selection query and for pinot_amd_execute_filter. */
+int pinot_amd_query_add_aggregation_filter_predicate(pinot_amd_query* q, int32_t agg_index, int32_t clause,
+                                                     const pinot_amd_predicate_spec* p, int32_t negate);
+/* QueryOptions filteredAggregationsSkipEmptyGroups (default 0). Non-zero and no aggregation without a filter: a
+ * group exists iff some doc matches the main filter AND (f1 OR ... OR fn), and pinot_amd_result_num_docs_matched
+ * counts those docs (FilteredGroupByOperator.java:116-180). With an unfiltered aggregation it changes nothing. */
+int pinot_amd_query_set_filtered_aggregations_skip_empty_groups(pinot_amd_query* q, int32_t skip);
 /* Install the group key space of group-by column `column` (values in the column's stored type, any
  * order; duplicates ignored): the union of the dictionaries of every server's segments, so that the
  * dense accumulator tables of all servers index groups identically and can be merged in place

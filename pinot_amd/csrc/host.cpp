@@ -1263,6 +1263,22 @@ struct pinot_amd_query {
   struct SelOrder { std::string column; int asc; };
   std::vector<SelOrder> sel_order;
   int64_t sel_limit = 10, sel_offset = 0;
+  // Filtered aggregations (AGG(x) FILTER (WHERE f), AggregationFunctionUtils.buildFilteredAggregationInfos):
+  // agg_filter[i] is the CNF of aggregation i's filter, its clauses numbered from 0 like the main filter's (shorter
+  // than aggs, or an empty entry: the main filter alone); skip_empty_groups: filteredAggregationsSkipEmptyGroups
+  std::vector<std::vector<PredSpec>> agg_filter;
+  int skip_empty_groups = 0;
+  const std::vector<PredSpec>* filter_of(size_t ai) const {
+    return ai < agg_filter.size() && !agg_filter[ai].empty() ? &agg_filter[ai] : nullptr;
+  }
+  size_t num_leaves() const {
+    size_t k = preds.size();
+    for (auto& f : agg_filter) k += f.size();
+    return k;
+  }
+  bool filtered() const {
+    return std::any_of(agg_filter.begin(), agg_filter.end(), [](const std::vector<PredSpec>& f) { return !f.empty(); });
+  }
 };
 
 extern "C" {
@@ -1277,22 +1293,26 @@ int pinot_amd_query_destroy(pinot_amd_query* q) {
   return 0;
 }
 
-int pinot_amd_query_add_predicate(pinot_amd_query* q, int32_t clause, const pinot_amd_predicate_spec* p,
-                                  int32_t negate) {
-  if (!q || !p || !p->column) return fail(PINOT_AMD_EINVAL, "add_predicate: bad arguments");
-  if (clause < 0 || clause >= kMaxClauses) return fail(PINOT_AMD_EUNSUPPORTED, "add_predicate: clause %d", clause);
-  if (q->preds.size() >= (size_t)kMaxLeaves) return fail(PINOT_AMD_EUNSUPPORTED, "add_predicate: too many predicates");
-  PredSpec s;
+// one leaf of a CNF (the main filter's or an aggregation filter's) from its ABI spec
+static int make_pred_spec(const char* what, pinot_amd_query* q, int32_t clause, const pinot_amd_predicate_spec* p,
+                          int32_t negate, PredSpec* out) {
+  if (!q || !p || !p->column) return fail(PINOT_AMD_EINVAL, "%s: bad arguments", what);
+  if (clause < 0 || clause >= kMaxClauses)
+    return fail(PINOT_AMD_EUNSUPPORTED, "%s: clause %d (at most %d clauses)", what, clause, kMaxClauses);
+  if (q->num_leaves() >= (size_t)kMaxLeaves)
+    return fail(PINOT_AMD_EUNSUPPORTED, "%s: too many predicates (the main filter and the aggregation filters share %d)",
+                what, kMaxLeaves);
+  PredSpec& s = *out;
   s.column = p->column;
   s.type = p->type;
   s.clause = clause;
   s.negate = negate ? 1 : 0;
   s.use_inv = p->use_inverted_index;
-  if (p->type < PINOT_AMD_EQ || p->type > PINOT_AMD_RANGE) return fail(PINOT_AMD_EINVAL, "add_predicate: bad type");
+  if (p->type < PINOT_AMD_EQ || p->type > PINOT_AMD_RANGE) return fail(PINOT_AMD_EINVAL, "%s: bad type", what);
   if (p->type != PINOT_AMD_RANGE) {
-    if (p->num_values < 1) return fail(PINOT_AMD_EINVAL, "add_predicate: no values");
+    if (p->num_values < 1) return fail(PINOT_AMD_EINVAL, "%s: no values", what);
     if ((p->type == PINOT_AMD_EQ || p->type == PINOT_AMD_NOT_EQ) && p->num_values != 1)
-      return fail(PINOT_AMD_EINVAL, "add_predicate: EQ takes one value");
+      return fail(PINOT_AMD_EINVAL, "%s: EQ takes one value", what);
     for (int i = 0; i < p->num_values; ++i) {
       if (p->h_values_i) s.vi.push_back(p->h_values_i[i]);
       if (p->h_values_d) s.vd.push_back(p->h_values_d[i]);
@@ -1310,7 +1330,33 @@ int pinot_amd_query_add_predicate(pinot_amd_query* q, int32_t clause, const pino
     if (p->lower_s) s.lower_s = p->lower_s;
     if (p->upper_s) s.upper_s = p->upper_s;
   }
+  return 0;
+}
+
+int pinot_amd_query_add_predicate(pinot_amd_query* q, int32_t clause, const pinot_amd_predicate_spec* p,
+                                  int32_t negate) {
+  PredSpec s;
+  if (int rc = make_pred_spec("add_predicate", q, clause, p, negate, &s)) return rc;
   q->preds.push_back(std::move(s));
+  return 0;
+}
+
+int pinot_amd_query_add_aggregation_filter_predicate(pinot_amd_query* q, int32_t agg_index, int32_t clause,
+                                                     const pinot_amd_predicate_spec* p, int32_t negate) {
+  const char* what = "add_aggregation_filter_predicate";
+  if (!q) return fail(PINOT_AMD_EINVAL, "%s: bad arguments", what);
+  if (agg_index < 0 || (size_t)agg_index >= q->aggs.size())
+    return fail(PINOT_AMD_EINVAL, "%s: aggregation index %d (the query has %zu)", what, agg_index, q->aggs.size());
+  PredSpec s;
+  if (int rc = make_pred_spec(what, q, clause, p, negate, &s)) return rc;
+  if (q->agg_filter.size() <= (size_t)agg_index) q->agg_filter.resize((size_t)agg_index + 1);
+  q->agg_filter[(size_t)agg_index].push_back(std::move(s));
+  return 0;
+}
+
+int pinot_amd_query_set_filtered_aggregations_skip_empty_groups(pinot_amd_query* q, int32_t skip) {
+  if (!q) return fail(PINOT_AMD_EINVAL, "set_filtered_aggregations_skip_empty_groups: null query");
+  q->skip_empty_groups = skip ? 1 : 0;
   return 0;
 }
 
@@ -1627,6 +1673,8 @@ struct pinot_amd_result {
   std::deque<Launch> launches;  // deque: Launch holds device buffers and is never moved
   std::vector<std::unique_ptr<DevBuf>> owned;  // leaf sets, remaps, bitsets
   bool filter_gate = false;  // the fused scan loads key / value columns behind its filter (JitPlan::filter_gate)
+  int nlanes = 1;            // filtered aggregations: the filter lanes of the scan, lane 0 (the main filter) included
+  const char* lane_table = "";  // ... and where that scan aggregates: regs / lds / cu / hbm / hash / hash+lds
   std::vector<std::string> slot_names;  // column of each slot (pinot_amd_result_packed_info)
   // inverted index leaves to (re)build each execution: (segment, leaf, container selection)
   struct InvLeaf {
@@ -1868,6 +1916,13 @@ static std::string plan_identity(const pinot_amd_query& Q, const std::vector<pin
     k += a.column + '\x1f';
     num(a.expr);
     k += a.column2 + '\x1f';
+  }
+  if (Q.filtered()) {  // the aggregation filters, literals included, per aggregation (hence each one's lane), and the option
+    k += "|AF" + std::to_string(Q.skip_empty_groups);
+    for (size_t ai = 0; ai < Q.aggs.size(); ++ai) {
+      k += '\x1c';
+      if (const std::vector<PredSpec>* f = Q.filter_of(ai)) k += preds_signature(*f);
+    }
   }
   k += "|O";
   for (const auto& o : Q.order_by) {
@@ -3273,7 +3328,8 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
 namespace {
 
 // accumulator request of the planner: the slot(s) and expression it reads, its operation and NaN rule
-struct AccReq { int slot; int op; int expr; int slot2; int nan_skip; };
+// (lane: the filter lane whose docs it takes, 0 = the main filter alone)
+struct AccReq { int slot; int op; int expr; int slot2; int nan_skip; int lane = 0; };
 
 // bytes per row a column's forward index holds
 double slot_bpr(const DevColumn& c) {
@@ -3318,6 +3374,14 @@ struct PlanBuild {
   std::vector<int> pred_slot;
   std::vector<size_t> order;
   int nclauses = 0;
+  // filter lanes (lanes): the main filter's predicates, then each lane's with its clauses renumbered behind the
+  // main ones; every later phase that reasons about "the filter" (the selectivity probe, the match-count cache,
+  // the inverted-index gate, the sampled counts) reads Qp->preds, the main filter alone
+  std::vector<PredSpec> all_preds;
+  std::vector<int> clause_lane;  // per clause of all_preds
+  std::vector<int> agg_lane;     // per aggregation of the query
+  int nlanes = 1;
+  bool lane_skip = false;        // filteredAggregationsSkipEmptyGroups with no unfiltered aggregation
   // key space, trims (keys_probe)
   double dense_keys = 1;
   std::vector<int64_t> seg_matched, seg_bound;
@@ -3355,6 +3419,7 @@ struct PlanBuild {
   int64_t lds_arrays();
 
   int raw_keys();
+  int lanes();
   int leaves();
   int keys_probe();
   int accs();
@@ -3420,6 +3485,55 @@ int PlanBuild::raw_keys() {
   return 0;
 }
 
+// Filter lanes (FilteredGroupByOperator's swim-lanes, AggregationFunctionUtils.buildFilteredAggregationInfos:407-420):
+// aggregations whose filters have the same signature share a lane; lane 0 is the main filter
+int PlanBuild::lanes() {
+  const pinot_amd_query& Q = *Qp;
+  all_preds = Q.preds;
+  int main_clauses = 0;
+  for (const PredSpec& p : Q.preds) main_clauses = std::max(main_clauses, p.clause + 1);
+  clause_lane.assign(main_clauses, 0);
+  agg_lane.assign(Q.aggs.size(), 0);
+  nlanes = 1;
+  if (!Q.filtered()) return 0;
+  std::vector<std::string> lane_sig(1);
+  bool any_unfiltered = false;
+  for (size_t ai = 0; ai < Q.aggs.size(); ++ai) {
+    const std::vector<PredSpec>* f = Q.filter_of(ai);
+    if (!f) {
+      any_unfiltered = true;
+      continue;
+    }
+    const std::string sig = preds_signature(*f);
+    int lane = 0;
+    for (int l = 1; l < nlanes; ++l)
+      if (lane_sig[l] == sig) lane = l;
+    if (!lane) {
+      lane = nlanes++;
+      lane_sig.push_back(sig);
+      std::map<int, int> renum;  // the filter's clause ids -> consecutive clauses behind the ones so far
+      for (const PredSpec& p : *f)
+        if (!renum.count(p.clause)) {
+          renum[p.clause] = (int)clause_lane.size();
+          clause_lane.push_back(lane);
+        }
+      for (PredSpec p : *f) {
+        p.clause = renum[p.clause];
+        all_preds.push_back(std::move(p));
+      }
+    }
+    agg_lane[ai] = lane;
+  }
+  if ((int)clause_lane.size() > kMaxClauses)
+    return fail(PINOT_AMD_EUNSUPPORTED, "filtered aggregations: %zu clauses (the main filter and every lane share %d)",
+                clause_lane.size(), kMaxClauses);
+  if (all_preds.size() > (size_t)kMaxLeaves)
+    return fail(PINOT_AMD_EUNSUPPORTED, "filtered aggregations: %zu predicates (the main filter and every lane share %d)",
+                all_preds.size(), kMaxLeaves);
+  lane_skip = Q.skip_empty_groups && !any_unfiltered;
+  return 0;
+}
+
 // the slot of a column the kernel must decode (added on first use)
 int PlanBuild::slot_of(const std::string& name) {
   for (size_t i = 0; i < slot_cols.size(); ++i)
@@ -3436,7 +3550,7 @@ int PlanBuild::leaves() {
       if (!s->cols.count(col)) return fail(PINOT_AMD_EINVAL, "segment %s has no column %s", s->name.c_str(), col.c_str());
       return 0;
     };
-    for (auto& p : Q.preds) if (int rc = need(p.column)) return rc;
+    for (auto& p : all_preds) if (int rc = need(p.column)) return rc;
     for (auto& g : Q.group_by) if (int rc = need(g)) return rc;
     for (auto& a : Q.aggs) {
       if (!a.column.empty()) if (int rc = need(a.column)) return rc;
@@ -3462,16 +3576,16 @@ int PlanBuild::leaves() {
   if (sel)
     for (auto& o : Q.sel_order) slot_of(o.column);
   // ---- per-segment leaves (PredicateEvaluatorProvider per segment) ----
-  np = Q.preds.size();
+  np = all_preds.size();  // the main filter's leaves, then the lanes'
   seg_leaves.assign(n, std::vector<DevLeaf>(np));
   std::vector<std::vector<int>> leaf_slot_col(n, std::vector<int>(np, -1));
   nclauses = 0;
-  for (size_t pi = 0; pi < np; ++pi) nclauses = std::max(nclauses, Q.preds[pi].clause + 1);
+  for (size_t pi = 0; pi < np; ++pi) nclauses = std::max(nclauses, all_preds[pi].clause + 1);
   // per predicate, once: whether its column is decoded anyway, and its leaf-cache key (the same on every segment)
   std::vector<char> pred_decoded(np, 0);
   std::vector<std::string> pred_key(np);
   for (size_t pi = 0; pi < np; ++pi) {
-    const PredSpec& p = Q.preds[pi];
+    const PredSpec& p = all_preds[pi];
     bool d = std::find(Q.group_by.begin(), Q.group_by.end(), p.column) != Q.group_by.end();
     for (auto& a : Q.aggs) d |= a.column == p.column || a.column2 == p.column;
     for (int sl = 0; sl < (int)slot_cols.size() && sel; ++sl) d |= slot_cols[sl] == p.column;
@@ -3480,7 +3594,7 @@ int PlanBuild::leaves() {
   }
   for (int si = 0; si < n; ++si) {
     for (size_t pi = 0; pi < np; ++pi) {
-      const PredSpec& p = Q.preds[pi];
+      const PredSpec& p = all_preds[pi];
       const Column& c = *segs[si]->cols.at(p.column);
       bool needs_slot = false;
       const bool decoded_anyway = pred_decoded[pi] != 0;
@@ -3707,7 +3821,9 @@ int PlanBuild::keys_probe() {
 
 int PlanBuild::push_acc(const AccReq& rq) {
   DevQuery& q = r->q;
-  if (nacc >= kMaxAcc) return fail(PINOT_AMD_EUNSUPPORTED, "too many aggregations");
+  if (nacc >= kMaxAcc)
+    return fail(PINOT_AMD_EUNSUPPORTED, "too many aggregations (at most %d accumulators, the filter lanes' counts included)",
+                kMaxAcc);
   acc_req[nacc] = rq;
   q.acc_op[nacc++] = rq.op;
   return 0;
@@ -3724,14 +3840,20 @@ int PlanBuild::accs() {
   auto find_req = [&](const AccReq& rq) -> int {
     for (size_t k = 0; k < reqs.size(); ++k)
       if (reqs[k].slot == rq.slot && reqs[k].op == rq.op && reqs[k].expr == rq.expr && reqs[k].slot2 == rq.slot2 &&
-          reqs[k].nan_skip == rq.nan_skip)
+          reqs[k].nan_skip == rq.nan_skip && reqs[k].lane == rq.lane)
         return (int)k;
     reqs.push_back(rq);
     return (int)reqs.size() - 1;
   };
   for (size_t ai = 0; ai < Q.aggs.size(); ++ai) {
     const AggSpec& a = Q.aggs[ai];
-    if (a.type == PINOT_AMD_AGG_COUNT) continue;
+    const int lane = agg_lane[ai];
+    // a lane's own count (a filtered COUNT, the count a filtered AVG divides by): a sum of 1 over the lane's docs
+    const AccReq lane_count{-1, ACC_SUM_I64, EXPR_ONE, -1, 0, lane};
+    if (a.type == PINOT_AMD_AGG_COUNT) {
+      if (lane) agg_req[ai] = find_req(lane_count);
+      continue;
+    }
     const Column& c = *segs[0]->cols.at(a.column);
     // SUM / AVG of integer values are summed exactly in 128 bits (SumAggregationFunction accumulates
     // in double: equal whenever partial sums stay below 2^53, and the correctly rounded exact sum
@@ -3756,23 +3878,24 @@ int PlanBuild::accs() {
     const int sl = slot_of(a.column);
     const int sl2 = a.expr != PINOT_AMD_EXPR_COLUMN ? slot_of(a.column2) : -1;
     if (a.type == PINOT_AMD_AGG_MINMAXRANGE) {
-      agg_req[ai] = find_req({sl, ACC_MIN, a.expr, sl2, 1});
-      agg_req2[ai] = find_req({sl, ACC_MAX, a.expr, sl2, 1});
+      agg_req[ai] = find_req({sl, ACC_MIN, a.expr, sl2, 1, lane});
+      agg_req2[ai] = find_req({sl, ACC_MAX, a.expr, sl2, 1, lane});
     } else {
-      agg_req[ai] = find_req({sl, op, a.expr, sl2, 0});
+      agg_req[ai] = find_req({sl, op, a.expr, sl2, 0, lane});
+      if (a.type == PINOT_AMD_AGG_AVG && lane) agg_req2[ai] = find_req(lane_count);  // AvgPair's count: the lane's
     }
   }
   std::vector<int> req_acc(reqs.size());
   acc_req.assign(kMaxAcc + 2, AccReq{0, 0, 0, -1, 0});
   nacc = 1;
   q.acc_op[0] = ACC_COUNT;
-  for (int sl = 0; sl < kMaxSlots; ++sl)
+  for (int sl = 0; sl <= kMaxSlots; ++sl)  // (the last round: the lanes' counts, which read no slot)
     for (size_t k = 0; k < reqs.size(); ++k)
-      if (reqs[k].slot == sl) {
+      if (reqs[k].slot == (sl < kMaxSlots ? sl : -1)) {
         req_acc[k] = nacc;
         if (int rc = push_acc(reqs[k])) return rc;
         if (reqs[k].op == ACC_SUM_I128)
-          if (int rc = push_acc({reqs[k].slot, ACC_HI, reqs[k].expr, reqs[k].slot2, 0})) return rc;
+          if (int rc = push_acc({reqs[k].slot, ACC_HI, reqs[k].expr, reqs[k].slot2, 0, reqs[k].lane})) return rc;
       }
   for (size_t ai = 0; ai < Q.aggs.size(); ++ai) {
     r->agg_type.push_back(Q.aggs[ai].type);
@@ -4115,12 +4238,20 @@ int PlanBuild::kernel_choices() {
     lds_max = std::min(lds_max, 160 * 1024);
   }
   base.nclauses = nclauses;
+  if (nlanes > 1) {
+    base.clause_lane = clause_lane;
+    base.clause_lane.resize(nclauses, 0);
+    base.nlanes = nlanes;
+    base.lane_skip = lane_skip;
+  }
   for (size_t j = 0; j < Q.group_by.size(); ++j) {
     base.group.push_back({slot_of(Q.group_by[j]), r->kind == PLAN_HASH ? 0 : r->key_stride[j]});
     for (int si = 0; si < n; ++si) base.any_remap |= hsegs[si].cols[slot_of(Q.group_by[j])].remap != nullptr;
   }
-  for (int a = 1; a < q.nacc; ++a)
+  for (int a = 1; a < q.nacc; ++a) {
     base.accs.push_back({q.acc_op[a], acc_req[a].slot, acc_req[a].expr, acc_req[a].slot2, acc_req[a].nan_skip});
+    base.accs.back().lane = acc_req[a].lane;
+  }
   base.num_keys = num_keys;
   base.admit = r->admit;
   base.seg_ord = seg_ord;
@@ -4152,7 +4283,8 @@ int PlanBuild::kernel_choices() {
     } else if (lds_bytes <= lds_max && !env_is("PINOT_AMD_WIDE_LDS", "0")) {
       base.lds = true;  // one CU-wide block (4 x 256 threads, 16 waves) owns the whole table
       base.scan_nsub = kPartSub;
-    } else if (!env_is("PINOT_AMD_PARTITIONED", "0") && !Q.group_by.empty()) {
+    } else if (!env_is("PINOT_AMD_PARTITIONED", "0") && !Q.group_by.empty() && nlanes == 1) {
+      // (a filtered query keeps the dense HBM table: a partition record carries no lane mask)
       // key space too large for an LDS table: partition the matching docs by key range and aggregate
       // each partition in LDS (random per-lane HBM atomics run ~17x below the coalesced rate)
       set_narrow((__int128)((all_docs + cus - 1) / cus));
@@ -4277,7 +4409,6 @@ int PlanBuild::kernel_choices() {
 }
 
 int PlanBuild::select_plan() {
-  const pinot_amd_query& Q = *Qp;
   DevQuery& q = r->q;
   // ---- selection-vector plan (late materialisation) ----
   // A selective filter over narrow rows: the select pass reads only the filter columns and appends the
@@ -4291,14 +4422,15 @@ int PlanBuild::select_plan() {
     if (pred_slot[pi] >= 0) leaf_slot[pred_slot[pi]] = true;
   for (auto& g : base.group) value_slot[g.first] = true;
   for (auto& a : base.accs)
-    if (a.op != ACC_FIRST_DOC) {
+    if (a.op != ACC_FIRST_DOC && a.slot >= 0) {
       value_slot[a.slot] = true;
       if (a.expr != EXPR_COL) value_slot[a.slot2] = true;
     }
   const char* sel_env = knob("PINOT_AMD_SELECT");
   // (a partitioned plan qualifies too: when its filter keeps few docs, the gather adds them straight into
   // the HBM table, where the partitioned plan would hand over to a fused direct-atomic scan of every row)
-  const bool sel_eligible = !filter_only && q.nacc > 0 && np > 0 && !r->trim && !r->admit && !r->seg_trim &&
+  // (filtered aggregations: neither the selection vector nor the filter gate carries a lane mask)
+  const bool sel_eligible = !filter_only && q.nacc > 0 && np > 0 && nlanes == 1 && !r->trim && !r->admit && !r->seg_trim &&
                             (r->kind == PLAN_DENSE || r->kind == PLAN_HASH || r->kind == PLAN_PARTITIONED) &&
                             !env_is("PINOT_AMD_SELECT_PARTITIONED", base.partitioned ? "0" : "-") &&
                             !(sel_env && !strcmp(sel_env, "never"));
@@ -4325,7 +4457,7 @@ int PlanBuild::select_plan() {
     {
       std::vector<int> gate(nclauses, 1), has(nclauses, 0);
       for (size_t k = 0; k < order.size(); ++k) {
-        const int c = Q.preds[order[k]].clause;
+        const int c = all_preds[order[k]].clause;
         has[c] = 1;
         for (int si = 0; si < n; ++si)
           if (hsegs[si].leaves[k].kind != LEAF_DOC_BITSET || hsegs[si].leaves[k].negate) gate[c] = 0;
@@ -4399,7 +4531,7 @@ int PlanBuild::select_plan() {
   // these scans run near the HBM rate already, and the gate's one tile per step and a-tile-ahead filter cost
   // more issue than the skipped sectors save.
   if (!base.select && r->kind == PLAN_DENSE && !base.partitioned && !r->admit && !filter_only && q.nacc > 0 && np > 0 &&
-      (env_is("PINOT_AMD_FILTER_GATE", "1") || env_is("PINOT_AMD_FILTER_GATE", "auto"))) {
+      nlanes == 1 && (env_is("PINOT_AMD_FILTER_GATE", "1") || env_is("PINOT_AMD_FILTER_GATE", "auto"))) {
     bool ok = true;  // docId-bitset leaves gate through the inverted-index path instead
     for (size_t k = 0; k < order.size() && ok; ++k)
       for (int si = 0; si < n; ++si) ok &= hsegs[si].leaves[k].kind != LEAF_DOC_BITSET;
@@ -4490,7 +4622,8 @@ int PlanBuild::select_plan() {
     // spill passes) instead of one HBM probe + atomics per doc; PINOT_AMD_HASH_SPILL=0 keeps the direct path
     int nval = 0;  // a spill record's value words (spill_agg_kernel holds at most 8 words of a record)
     for (const JitAcc& a : base.accs) nval += a.op != ACC_HI && a.op != ACC_FIRST_DOC;
-    const bool spill = !env_is("PINOT_AMD_HASH_SPILL", "0") && base.hash_words + nval <= 8;
+    // (not for filtered aggregations: a spilled record carries no lane mask)
+    const bool spill = !env_is("PINOT_AMD_HASH_SPILL", "0") && base.hash_words + nval <= 8 && nlanes == 1;
     const int64_t reserve = 1024 + (spill ? (int64_t)kSpillMaxParts * 4 + 16 : 0);
     // as many slots as the LDS holds beside the kernel's static LDS (counters), a multiple of 64
     int64_t S = env_i64("PINOT_AMD_HASH_LDS_SLOTS", 0);
@@ -4683,7 +4816,6 @@ int PlanBuild::launch_segments(LaunchBuild& lb) {
 // the launch's kernel shape: slots and leaves as the segments of the launch allow, the pipeline depth, the
 // partitioned scatter's staging, and the launch's algorithmic bytes
 int PlanBuild::launch_shape(LaunchBuild& lb) {
-  const pinot_amd_query& Q = *Qp;
   Launch& L = lb.L;
   std::vector<DevSegment>& ls = lb.ls;
   JitPlan& jp = lb.jp;
@@ -4720,7 +4852,7 @@ int PlanBuild::launch_shape(LaunchBuild& lb) {
     jp.slots.push_back(js);
   }
   for (size_t k = 0; k < order.size(); ++k) {
-    JitLeaf jl{pred_slot[order[k]], Q.preds[order[k]].clause, ls[0].leaves[k].negate, 0u};
+    JitLeaf jl{pred_slot[order[k]], all_preds[order[k]].clause, ls[0].leaves[k].negate, 0u};
     bool small_sets = jl.slot >= 0;
     for (auto& d : ls) {
       jl.kinds |= 1u << d.leaves[k].kind;
@@ -4816,7 +4948,7 @@ int PlanBuild::launch_shape(LaunchBuild& lb) {
     std::vector<int> gate(nclauses, 1), has(nclauses, 0);
     for (const JitLeaf& jl : jp.leaves) {
       has[jl.clause] = 1;
-      if (jl.kinds != (1u << LEAF_DOC_BITSET) || jl.negate) gate[jl.clause] = 0;
+      if (jl.kinds != (1u << LEAF_DOC_BITSET) || jl.negate || jp.lane_of(jl.clause) > 0) gate[jl.clause] = 0;
     }
     for (int c = 0; c < nclauses; ++c) L.gated |= gate[c] && has[c];
     if (jp.filter_gate) {  // filter columns of every doc, the key / value columns of the matching docs
@@ -5388,6 +5520,27 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
   if (sel && (!qq->aggs.empty() || !qq->group_by.empty()))
     return fail(PINOT_AMD_EINVAL, "execute: a selection query takes no aggregation and no GROUP BY");
   if (sel && !qq->key_space.empty()) return fail(PINOT_AMD_EINVAL, "execute: a selection query takes no key space");
+  const bool filtered = qq->filtered();
+  if (filtered && (filter_only || sel))
+    return fail(PINOT_AMD_EINVAL, "execute: aggregation filters (FILTER (WHERE ...)) on a %s",
+                sel ? "selection query" : "filter-only execution");
+  if (filtered && !qq->group_by.empty() && qq->limit >= 0 && !qq->order_by.empty()) {
+    // segment-level trims order a segment's groups by values no lane-wise scan has per segment (as execute_distinct)
+    std::vector<bool> seen(qq->group_by.size(), false);
+    bool safe = true;
+    for (const auto& ob : qq->order_by) {
+      if (ob.kind != 0) safe = false;
+      else seen[ob.index] = true;
+    }
+    safe = safe && std::all_of(seen.begin(), seen.end(), [](bool b) { return b; });
+    if (safe && qq->limit >= qq->sort_agg_threshold && !qq->server_final)
+      return fail(PINOT_AMD_EUNSUPPORTED, "filtered aggregations with a segment-level safe trim (ORDER BY = GROUP BY, LIMIT "
+                                          "%lld >= sortAggregateLimitThreshold %lld)",
+                  (long long)qq->limit, (long long)qq->sort_agg_threshold);
+    if (!safe && qq->min_seg_trim > 0)
+      return fail(PINOT_AMD_EUNSUPPORTED, "filtered aggregations with a segment-level trim (minSegmentGroupTrimSize %lld)",
+                  (long long)qq->min_seg_trim);
+  }
   const std::string plan_key = plan_identity(*qq, segs, filter_only);
   if (pinot_amd_result* hit = plan_cache_take(plan_key)) {  // a prepared plan of this identity: run it
     std::unique_ptr<pinot_amd_result> hold(hit);
@@ -5416,10 +5569,18 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
   b.r = r;
   if (int rc = b.raw_keys()) return rc;
   clk.mark("raw_keys");
+  if (int rc = b.lanes()) return rc;
   if (int rc = b.leaves()) return rc;
   clk.mark("leaves");
   if (int rc = b.keys_probe()) return rc;
   clk.mark("keys_probe");
+  // Pinot admits groups across the lanes in the iteration order of a HashMap<FilterContext, ...>
+  // (AggregationFunctionUtils.java:407, 448): once a segment can reach numGroupsLimit its result is unspecified
+  if (b.nlanes > 1 && b.limit_possible)
+    return fail(PINOT_AMD_EUNSUPPORTED, "filtered aggregations where a segment may reach numGroupsLimit (%lld): the "
+                                        "reference's result is unspecified there; raise numGroupsLimit",
+                (long long)qq->num_groups_limit);
+  r->nlanes = b.nlanes;
   if (int rc = b.accs()) return rc;
   clk.mark("accs");
   if (int rc = b.plan_kind()) return rc;
@@ -5432,6 +5593,10 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
   clk.mark("kernel_choices");
   if (int rc = b.select_plan()) return rc;
   clk.mark("select_plan");
+  r->lane_table = b.base.group.empty() ? "regs"
+                  : b.base.hash        ? (b.base.hash_lds > 0 ? "hash+lds" : "hash")
+                  : b.base.lds         ? (b.base.scan_nsub > 1 ? "cu" : "lds")
+                                       : "hbm";
   if (int rc = b.group_launches()) return rc;
   if (int rc = b.plan_launches()) return rc;
   if (int rc = b.alloc_buffers()) return rc;
@@ -5614,6 +5779,12 @@ static int execute_distinct(pinot_amd_query* qq, pinot_amd_segment* const* segs_
 
 int pinot_amd_execute(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, int32_t n, void* stream,
                       pinot_amd_result** out) {
+  if (qq && qq->filtered())
+    for (size_t ai = 0; ai < qq->aggs.size(); ++ai)
+      if (is_value_set_agg(qq->aggs[ai].type))
+        return fail(PINOT_AMD_EUNSUPPORTED, "%s: the value-set queries of DISTINCTCOUNT / PERCENTILE / DISTINCTSUM / "
+                                            "DISTINCTAVG do not take the lanes' predicates",
+                    qq->filter_of(ai) ? "FILTER on a value-set aggregation" : "filtered aggregations beside a value-set aggregation");
   if (qq && std::any_of(qq->aggs.begin(), qq->aggs.end(),
                         [](const AggSpec& a) { return is_value_set_agg(a.type); }))
     return no_throw("execute", [&] { return execute_distinct(qq, segs_in, n, stream, out); });
@@ -5946,6 +6117,8 @@ static std::string kernel_info_of(pinot_amd_result* r) {
     info += seq ? "+admit-seq" : "+admit";
   }
   if (r->launches.size() > 1) info += " x" + std::to_string(r->launches.size());
+  if (r->nlanes > 1)  // filtered aggregations: the filter lanes and the table their scan aggregates into
+    info += " +lanes(" + std::to_string(r->nlanes - 1) + ") table=" + r->lane_table;
   if (r->dc)  // the plan that served each DISTINCTCOUNT column's value sets
     for (DistinctFold::Child& ch : r->dc->children) info += " +distinct(" + ch.column + ":" + kernel_info_of(ch.r) + ")";
   return info;
@@ -6224,13 +6397,14 @@ static void final_value(const pinot_amd_result* r, const uint64_t* A, int a, dou
   };
   switch (r->agg_type[a]) {
     case PINOT_AMD_AGG_COUNT:
-      vi = (int64_t)cnt;
+      vi = (int64_t)(acc ? w : cnt);  // (a filtered COUNT: its lane's count accumulator)
       v = (double)vi;
       break;
     case PINOT_AMD_AGG_AVG: {
       int64_t ex;
       const double s = op == ACC_SUM_F64 ? ([&] { double d; memcpy(&d, &w, 8); return d; })() : sum128(&ex);
-      v = cnt ? s / (double)cnt : -INFINITY;  // AvgAggregationFunction: empty -> DEFAULT_FINAL_RESULT
+      const uint64_t n = r->agg_acc2[a] ? A[r->agg_acc2[a]] : cnt;  // (a filtered AVG: its lane's count)
+      v = n ? s / (double)n : -INFINITY;  // AvgAggregationFunction: empty -> DEFAULT_FINAL_RESULT
       break;
     }
     case PINOT_AMD_AGG_MIN:
@@ -6427,7 +6601,7 @@ int pinot_amd_result_fetch_intermediate(pinot_amd_result* r, int64_t cap, double
       const int acc = r->agg_acc[a];
       switch (r->agg_type[a]) {
         case PINOT_AMD_AGG_AVG: {  // AvgPair(sum, count)
-          const double cnt = (double)(r->q.nacc ? A[0] : 0);
+          const double cnt = (double)(r->agg_acc2[a] ? A[r->agg_acc2[a]] : r->q.nacc ? A[0] : 0);  // (filtered: the lane's)
           if (r->q.acc_op[acc] == ACC_SUM_F64) memcpy(&out[0], &A[acc], 8);
           else out[0] = (double)(__int128)(((unsigned __int128)A[acc + 1] << 64) | (unsigned __int128)A[acc]);
           out[1] = cnt;

@@ -54,8 +54,9 @@ struct JitLeaf {
   int lut = 0;
 };
 // value an accumulator reads: a column slot, or a binary arithmetic expression of two slots
-// (EXPR_MUL / SUB / ADD: Pinot's times / minus / plus transforms)
-enum { EXPR_COL = 0, EXPR_MUL = 1, EXPR_SUB = 2, EXPR_ADD = 3 };
+// (EXPR_MUL / SUB / ADD: Pinot's times / minus / plus transforms); EXPR_ONE: the constant 1, no slot read
+// (slot -1) -- an ACC_SUM_I64 of it is a filter lane's own doc count, merged as an addition everywhere
+enum { EXPR_COL = 0, EXPR_MUL = 1, EXPR_SUB = 2, EXPR_ADD = 3, EXPR_ONE = 4 };
 struct JitVal {
   int expr = EXPR_COL;
   int slot = 0;
@@ -78,12 +79,24 @@ struct JitAcc {
   // word -- no returned value to wait for the carry -- and the plan sets each high word to the low word's
   // sign at its end (sext_hi_kernel), the 128-bit sum the readers expect
   int hbm_narrow = 0;
+  // filter lane (JitPlan::clause_lane): the accumulator takes the docs of `match` that also pass every clause of
+  // this lane (0: the main filter alone)
+  int lane = 0;
   JitVal val() const { return JitVal{expr, slot, slot2}; }
 };
 struct JitPlan {
   std::vector<JitSlot> slots;
   std::vector<JitLeaf> leaves;  // in DevSegment::leaves order
   int nclauses = 0;
+  // Filtered aggregations (AGG(x) FILTER (WHERE f), FilteredGroupByOperator's swim-lanes): clause c belongs to
+  // lane clause_lane[c] (empty: every clause is the main filter's, lane 0). `match` is AND-ed with the lane-0
+  // clauses only; lane f > 0 gets the mask F<f> = match & its clauses, and an accumulator of lane f is guarded by
+  // F<f> instead of match. A lane clause gates no load and clears no bit of match -- but for lane_skip
+  // (filteredAggregationsSkipEmptyGroups with only filtered aggregations): match &= F1 | ... | Fn once they are known.
+  std::vector<int> clause_lane;
+  int nlanes = 1;  // lanes including lane 0
+  bool lane_skip = false;
+  int lane_of(int c) const { return c < (int)clause_lane.size() ? clause_lane[c] : 0; }
   std::vector<std::pair<int, int64_t>> group;  // (slot, key stride)
   bool any_remap = false;
   std::vector<JitAcc> accs;  // accumulators 1..n (0 is COUNT), in DevQuery acc order

@@ -28,8 +28,8 @@ import numpy as np
 from . import _lib
 from ._lib import ColumnSpec, KeyTransformSpec, PredicateSpec, check, lib
 from .query import (KEY_TRANSFORMS, TIME_UNITS, TRUNC_UNITS, VALUE_SET_FUNCS, DistinctSize, FinalValue, JavaDouble,
-                    QueryContext, fold_distinct_count, hists_from_csr, key_transform, parse_sql, reduce_rows,
-                    server_table, sets_from_csr, split_distinct_count)
+                    QueryContext, filter_text, fold_distinct_count, hists_from_csr, key_transform, parse_sql, reduce_rows,
+                    server_table, sets_from_csr, split_distinct_count, to_cnf)
 from .segment import ColumnBuffers, SegmentBuffers, DOUBLE, FLOAT, INT, LONG, STRING
 
 TYPE_CODE = {INT: 0, LONG: 1, FLOAT: 2, DOUBLE: 3, STRING: 4}
@@ -292,7 +292,8 @@ class QueryResult:
     def kernel_info(self) -> str:
         """The device plan: 'jit' (fused scan), 'jit-select' / 'jit-wselect' (selection vector; the
         filter on 4-doc tiles / 64-doc bitset words), 'jit-partitioned', 'jit-hash', 'jit-hash-trim';
-        ' xN' when the batch ran as N shape launches."""
+        ' xN' when the batch ran as N shape launches; ' +lanes(n) table=regs|lds|cu|hbm|hash|hash+lds' for a query
+        with filtered aggregations: its n filter lanes and the table its scan aggregates into."""
         return lib().pinot_amd_result_kernel_info(self._h).decode()
 
     def packed_info(self) -> str:
@@ -680,6 +681,14 @@ class ServerQueryExecutor:
         its global key space (dist.global_key_space: the union of every rank's dictionaries), so that
         every rank's dense group table indexes the same groups."""
         qc = parse_sql(query) if isinstance(query, str) else query
+        if qc.has_filtered_aggregations():
+            if key_space is not None:
+                raise _lib.PinotAmdError("a query with filtered aggregations (FILTER (WHERE ...)) takes no key_space: the "
+                                         "cross-rank merge does not cover it")
+            for a in qc.aggregations:  # (distinct_count="native": the library refuses it, EUNSUPPORTED)
+                if a.func in VALUE_SET_FUNCS and self.distinct_count != "native":
+                    raise _lib.PinotAmdError(f"FILTER (WHERE ...) in a query with {a.func} is not supported: the value-set "
+                                             "queries do not take the lanes' predicates")
         if qc.is_selection():
             if key_space is not None:
                 raise _lib.PinotAmdError("a selection query takes no key_space (its rows merge by value at the broker)")
@@ -778,6 +787,9 @@ class ServerQueryExecutor:
                 if key_space is not None and g in key_space:
                     self._set_key_space(qh, g, first.columns[g].stored_type, key_space[g])
             check(L.pinot_amd_query_set_num_groups_limit(qh, qc.num_groups_limit), "set_num_groups_limit")
+            if qc.filtered_aggregations_skip_empty_groups:
+                check(L.pinot_amd_query_set_filtered_aggregations_skip_empty_groups(qh, 1),
+                      "set_filtered_aggregations_skip_empty_groups")
             if server_trim and qc.group_by:
                 check(L.pinot_amd_query_set_result_limit(qh, qc.limit, qc.min_server_group_trim_size,
                                                          qc.group_trim_threshold), "set_result_limit")
@@ -787,8 +799,11 @@ class ServerQueryExecutor:
             native = []
             agg_slots = []
 
-            def add(func, column, expr=None, param=None):
+            def add(func, column, expr=None, param=None, filt=None):
+                # (a filtered aggregation: its lane -- the filter's text -- is part of the library aggregation's identity)
                 key = (func, column) if param is None else (func, column, param)
+                if filt is not None:
+                    key += ("FILTER", filter_text(filt))
                 if key in native:
                     return native.index(key)
                 idx = C.c_int32()
@@ -803,34 +818,44 @@ class ServerQueryExecutor:
                     check(L.pinot_amd_query_add_aggregation_expr(qh, AGG_CODE[func], EXPR_CODE[expr[0]],
                                                                  expr[1].encode(), expr[2].encode(), C.byref(idx)),
                           f"add_aggregation_expr({func} {column})")
+                for ci, clause in enumerate(to_cnf(filt)):
+                    for pred, neg in clause:
+                        col = first.columns.get(pred.column)
+                        if col is None:
+                            raise _lib.PinotAmdError(f"unknown column {pred.column!r} in segment {first.name}")
+                        spec = _predicate_spec(pred, col, self.use_inverted_index, keep)
+                        check(L.pinot_amd_query_add_aggregation_filter_predicate(qh, idx.value, ci, C.byref(spec),
+                                                                                 1 if neg else 0),
+                              "add_aggregation_filter_predicate")
                 native.append(key)
                 return idx.value
 
             for a in qc.aggregations:
                 if a.func == "AVG":
-                    agg_slots.append(("avg", add("SUM", a.column, a.expr), add("COUNT", "*")))
+                    # (with FILTER: the sum and the count of the aggregation's lane)
+                    agg_slots.append(("avg", add("SUM", a.column, a.expr, None, a.filter), add("COUNT", "*", None, None, a.filter)))
                 elif a.func == "DISTINCTCOUNT":  # the library folds the value sets (distinct_count="native")
                     col = first.columns.get(a.column)
                     if col is None:
                         raise _lib.PinotAmdError(f"unknown column {a.column!r} in segment {first.name}")
-                    agg_slots.append(("distinct", add("DISTINCTCOUNT", a.column), col.stored_type))
+                    agg_slots.append(("distinct", add("DISTINCTCOUNT", a.column, None, None, a.filter), col.stored_type))
                 elif a.func in VALUE_SET_FUNCS:    # PERCENTILE / DISTINCTSUM / DISTINCTAVG, likewise
                     col = first.columns.get(a.column)
                     if col is None:
                         raise _lib.PinotAmdError(f"unknown column {a.column!r} in segment {first.name}")
                     agg_slots.append(("hist" if a.func == "PERCENTILE" else "dset",
-                                      add(a.func, a.column, None, a.param), col.stored_type))
+                                      add(a.func, a.column, None, a.param, a.filter), col.stored_type))  # (a FILTER: refused there)
                 elif a.func == "MINMAXRANGE":  # MinMaxRangePair (min, max), NaN-skipping, in the library
-                    agg_slots.append(("range", add("MINMAXRANGE", a.column, a.expr)))
+                    agg_slots.append(("range", add("MINMAXRANGE", a.column, a.expr, None, a.filter)))
                 else:
-                    agg_slots.append(("direct", add(a.func, a.column, a.expr)))
+                    agg_slots.append(("direct", add(a.func, a.column, a.expr, None, a.filter)))
             if not qc.aggregations and qc.group_by:
                 add("COUNT", "*")  # DISTINCT-style group-by still needs the group presence count
             if server_trim and qc.group_by:
                 for kind, idx, asc in qc.order_by_targets():
                     if kind == 1:  # the library aggregation whose final value orders (AVG: sum / count)
                         a = qc.aggregations[idx]
-                        idx = add(a.func, a.column, a.expr, a.param)
+                        idx = add(a.func, a.column, a.expr, a.param, a.filter)
                     check(L.pinot_amd_query_add_order_by(qh, kind, idx, 1 if asc else 0), "add_order_by")
             arr = (C.c_void_p * len(segments))(*[s.handle.value for s in segments])
             rh = C.c_void_p()

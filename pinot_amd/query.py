@@ -105,6 +105,36 @@ def to_cnf(f: Optional[FilterContext]) -> List[List[Leaf]]:
     return cnf(nnf(f, False))
 
 
+def _literal_text(v) -> str:
+    """A predicate literal as the reference's predicates hold it (a string): 9999 -> 9999, 1.5 -> 1.5."""
+    return v if isinstance(v, str) else repr(v)
+
+
+def predicate_text(p: Predicate) -> str:
+    """EqPredicate / NotEqPredicate / InPredicate / NotInPredicate / RangePredicate.toString."""
+    if p.type in ("EQ", "NOT_EQ"):
+        return f"{p.column} {'=' if p.type == 'EQ' else '!='} '{_literal_text(p.values[0])}'"
+    if p.type in ("IN", "NOT_IN"):
+        vals = ",".join(f"'{_literal_text(v)}'" for v in p.values)
+        return f"{p.column} {'IN' if p.type == 'IN' else 'NOT IN'} ({vals})"
+    lo = None if p.lower is None else f"{p.column} {'>=' if p.lower_inclusive else '>'} '{_literal_text(p.lower)}'"
+    hi = None if p.upper is None else f"{p.column} {'<=' if p.upper_inclusive else '<'} '{_literal_text(p.upper)}'"
+    if lo is None or hi is None:
+        return hi if lo is None else lo
+    if p.lower_inclusive and p.upper_inclusive:
+        return f"{p.column} BETWEEN '{_literal_text(p.lower)}' AND '{_literal_text(p.upper)}'"
+    return f"({lo} AND {hi})"
+
+
+def filter_text(f: FilterContext) -> str:
+    """FilterContext.toString: what getResultColumnName prints after FILTER(WHERE."""
+    if f.type == "PREDICATE":
+        return predicate_text(f.predicate)
+    if f.type == "NOT":
+        return f"(NOT {filter_text(f.children[0])})"
+    return "(" + f" {f.type} ".join(filter_text(c) for c in f.children) + ")"
+
+
 EXPR_OPS = {"*": "MUL", "-": "SUB", "+": "ADD"}
 EXPR_FUNC = {"MUL": "times", "SUB": "minus", "ADD": "plus"}
 
@@ -154,11 +184,21 @@ class Aggregation:
     alias: Optional[str] = None
     expr: Optional[Tuple[str, str, str]] = None
     param: Optional[float] = None   # PERCENTILE: the percentile, 0 <= param <= 100
+    # AGG(...) FILTER (WHERE filter): the aggregation takes the docs matching the query's filter AND this one
+    # (AggregationFunctionUtils.buildFilteredAggregationInfos); None: the query's filter alone
+    filter: Optional[FilterContext] = None
 
     @property
     def text(self) -> str:
-        """The function's canonical text (what ORDER BY names when there is no alias)."""
-        return agg_text(self.func, self.column, self.param)
+        """The function's canonical text (what ORDER BY names when there is no alias); a filtered aggregation's is
+        AggregationFunctionUtils.getResultColumnName: ``sum(x) FILTER(WHERE x > '9999')``."""
+        t = agg_text(self.func, self.column, self.param)
+        return t if self.filter is None else f"{t} FILTER(WHERE {filter_text(self.filter)})"
+
+    @property
+    def cnf(self) -> List[List[Leaf]]:
+        """The aggregation filter in conjunctive normal form ([] without one)."""
+        return to_cnf(self.filter)
 
     @property
     def name(self) -> str:
@@ -312,6 +352,11 @@ class QueryContext:
     server_return_final_result: bool = False
     sort_aggregate_limit_threshold: int = 10_000
     offset: int = 0                     # LIMIT n OFFSET m / LIMIT m, n (the broker applies it; a server keeps offset + limit)
+    # filteredAggregationsSkipEmptyGroups: with only filtered aggregations, a group exists iff some lane has a doc
+    filtered_aggregations_skip_empty_groups: bool = False
+
+    def has_filtered_aggregations(self) -> bool:
+        return any(a.filter is not None for a in self.aggregations)
 
     def is_selection(self) -> bool:
         """SELECT columns [ORDER BY ...] LIMIT n: neither aggregations nor GROUP BY (SelectionPlanNode)."""
@@ -496,13 +541,14 @@ class _Parser:
                         col = f"{EXPR_FUNC[op]}({col},{col2})"
                 param = self.percentile_arg(func, param)
                 self.eat_op(")")
+                agg_filter = self.agg_filter()
                 alias = None
                 if self.kw("AS"):
                     self.i += 1
                     alias = self.ident()
                 elif self.peek()[0] == "id" and self.peek()[1].upper() not in ("FROM",):
                     alias = self.ident()   # implicit alias: sum(x) revenue
-                aggs.append(Aggregation(func, col, alias, expr, param))
+                aggs.append(Aggregation(func, col, alias, expr, param, agg_filter))
             elif tok == ("op", "*"):
                 self.i += 1
                 cols.append("*")
@@ -554,6 +600,25 @@ class _Parser:
                 raise ValueError(f"{c} is not a GROUP BY key of the query")
         return QueryContext(table, aggs, group_by, flt, order, limit, cols, offset=offset)
 
+    def agg_filter(self) -> Optional[FilterContext]:
+        """FILTER (WHERE <expr>) behind an aggregation call, or None."""
+        if not (self.kw("FILTER") and self.peek(1) == ("op", "(")):
+            return None
+        self.i += 2
+        self.eat_kw("WHERE")
+        if self.peek() == ("op", ")"):
+            raise ValueError("FILTER (WHERE ...) needs an expression")
+        depth, k = 1, 0
+        while depth and self.peek(k)[0] != "eof":  # the clause's tokens: a key transform is no filter column
+            tok = self.peek(k)
+            if tok[0] == "id" and tok[1].replace("_", "").lower() in KEY_TRANSFORMS and self.peek(k + 1) == ("op", "("):
+                raise ValueError(f"FILTER (WHERE ...) on the key transform {tok[1]} is not supported")
+            depth += (tok == ("op", "(")) - (tok == ("op", ")"))
+            k += 1
+        f = self.expr()
+        self.eat_op(")")
+        return f
+
     def count(self, what: str) -> int:
         v = self.literal()
         if not isinstance(v, int) or v < 0:
@@ -602,6 +667,9 @@ class _Parser:
             param = self.percentile_arg(func, param)
             self.eat_op(")")
             expr = agg_text(func, col, param)
+            f = self.agg_filter()
+            if f is not None:  # a filtered aggregation named by its result column text
+                expr += f" FILTER(WHERE {filter_text(f)})"
         else:
             expr = self.key_item()
         asc = True
@@ -740,6 +808,8 @@ def _parse_sql(sql: str) -> QueryContext:
             qc.sort_aggregate_limit_threshold = int(v)
         elif k.lower() == "minsegmentgrouptrimsize":
             qc.min_segment_group_trim_size = int(v)
+        elif k.lower() == "filteredaggregationsskipemptygroups":
+            qc.filtered_aggregations_skip_empty_groups = v.strip().lower() == "true"
     return qc
 
 
@@ -803,6 +873,9 @@ def split_distinct_count(qc: QueryContext):
     group is one group of that query. PERCENTILE, DISTINCTSUM and DISTINCTAVG read the same query (its COUNT is
     the number of docs holding the value: the group's histogram), so every such aggregation on one column shares
     one sub query, listed under the first of them. Returns (base query, [(aggregation index, sub query)])."""
+    if qc.has_filtered_aggregations():
+        raise ValueError("FILTER (WHERE ...) in a query with DISTINCTCOUNT / PERCENTILE / DISTINCTSUM / DISTINCTAVG is "
+                         "not supported: the value-set queries do not take the lanes' predicates")
     rest = [a for a in qc.aggregations if a.func not in VALUE_SET_FUNCS]
     base = dataclasses.replace(qc, aggregations=rest or [Aggregation("COUNT", "*")], order_by=[])
     subs = []
