@@ -47,7 +47,8 @@ enum pinot_amd_data_type { PINOT_AMD_INT = 0, PINOT_AMD_LONG = 1, PINOT_AMD_FLOA
 enum pinot_amd_fwd_encoding {
   PINOT_AMD_FWD_FIXED_BIT = 0, /* dict-encoded SV, unsorted: FixedBitSVForwardIndexReaderV2 */
   PINOT_AMD_FWD_RAW = 1,       /* raw fixed-width SV: FixedBytePower2ChunkSV / FixedByteChunkSV (PASS_THROUGH) */
-  PINOT_AMD_FWD_SORTED = 2     /* dict-encoded SV, sorted: SortedIndexReaderImpl */
+  PINOT_AMD_FWD_SORTED = 2,    /* dict-encoded SV, sorted: SortedIndexReaderImpl */
+  PINOT_AMD_FWD_FIXED_BIT_MV = 3 /* dict-encoded MV: FixedBitMVForwardIndexReader (pinot_amd_segment_add_mv_column) */
 };
 
 /* Predicate types (pinot-common/.../request/context/predicate/Predicate.java Type) */
@@ -82,7 +83,17 @@ enum pinot_amd_agg_type { PINOT_AMD_AGG_COUNT = 0, PINOT_AMD_AGG_SUM = 1, PINOT_
                           PINOT_AMD_AGG_DISTINCTSUM = 9,
                           /* DistinctAvgAggregationFunction.java:83-95: that sum over the set's size (0.0 / 0 =
                            * NaN for an empty set) */
-                          PINOT_AMD_AGG_DISTINCTAVG = 10 };
+                          PINOT_AMD_AGG_DISTINCTAVG = 10,
+                          /* The multi-value aggregations (CountMV / SumMV / MinMV / MaxMV / AvgMV /
+                           * MinMaxRangeMVAggregationFunction: the aggregateMV bodies of their SV parents) over one
+                           * multi-value INT / LONG / FLOAT / DOUBLE column: every value of a matching doc counts.
+                           * Added with pinot_amd_query_add_aggregation_mv (they take no literal). COUNTMV: the
+                           * number of values; SUMMV: their sum as doubles; MINMV / MAXMV: value < min / value > max
+                           * from +inf / -inf (NaN never enters, with and without GROUP BY); AVGMV: the AvgPair (sum
+                           * of values, count of values); MINMAXRANGEMV: the pair (min, max), final max - min. No
+                           * matching doc: 0, 0.0, +inf, -inf, -inf, -inf. See "Multi-value columns" below. */
+                          PINOT_AMD_AGG_COUNTMV = 11, PINOT_AMD_AGG_SUMMV = 12, PINOT_AMD_AGG_MINMV = 13,
+                          PINOT_AMD_AGG_MAXMV = 14, PINOT_AMD_AGG_AVGMV = 15, PINOT_AMD_AGG_MINMAXRANGEMV = 16 };
 
 /* ------------------------------------------------------------------------------------------------
  * Runtime
@@ -128,12 +139,53 @@ int pinot_amd_segment_create(const char* name, int64_t num_docs, pinot_amd_segme
  * and GZIP chunks are inflated on the host with the system libzstd / zlib. Malformed chunks fail
  * with PINOT_AMD_EINVAL. */
 int pinot_amd_segment_add_column(pinot_amd_segment* seg, const pinot_amd_column_spec* spec);
+/* Multi-value columns: a dictionary-encoded MV forward index as FixedBitMVForwardIndexWriter writes it
+ * (local/io/writer/impl/FixedBitMVForwardIndexWriter.java:36-101,143-158, read by FixedBitMVForwardIndexReader.java:66-141),
+ * all big-endian: numChunks int32 chunk offsets (docsPerChunk = ceil(2048 / (float) (totalNumValues / numDocs)), the
+ * inner division Java's int division; entry k = the value index where doc k * docsPerChunk starts), a bitmap of
+ * ceil(totalNumValues / 8) bytes, MSB-first (bit i set = value i starts a doc; every doc has at least one value), and
+ * the fixed-bit dictId stream of ceil(totalNumValues * bits / 8) bytes. spec->encoding is PINOT_AMD_FWD_FIXED_BIT_MV,
+ * h_dictionary is required and h_fwd / fwd_size are that whole file (V1 <col>.mv.fwd, V3 <col>.forward_index);
+ * total_num_values / max_num_values_per_doc are ColumnMetadata's totalNumberOfEntries / maxNumberOfMultiValues. The
+ * bytes are copied (padded) and validated on the device: EINVAL when the sizes do not match the formula, the bitmap's
+ * popcount is not numDocs, bit 0 is unset, a chunk offset disagrees with the bitmap's rank, or a doc is longer than
+ * max_num_values_per_doc. The one derived index is the rank of the first value of every 4096-value tile (one int32 per
+ * tile). A segment of 0 docs takes an empty forward index. h_inverted: EUNSUPPORTED (inverted indexes on MV columns are
+ * not on the path); raw (no-dictionary) MV forward indexes cannot be staged. pinot_amd_segment_add_column with
+ * PINOT_AMD_FWD_FIXED_BIT_MV: EINVAL (use this call).
+ *
+ * Queries over an MV column:
+ *   filters        EQ / IN / RANGE match a doc iff any of its values matches; NOT_EQ / NOT_IN (and negate = 1 on an
+ *                  EQ / IN leaf) iff no value is in the excluded set (BaseDictionaryBasedPredicateEvaluator.applyMV,
+ *                  PredicateType.isExclusive); leaves are independent (c > 5 AND c < 2 matches a doc holding 1 and 7).
+ *                  Each MV leaf becomes a dense docId bitset per segment, built inside the execution where the
+ *                  inverted-index expansion runs (pinot_amd_execute_again and last_kernel_ms cover it);
+ *                  algorithmic_bytes adds total_values * (bits + 1) / 8 and the bitset written and read once.
+ *   aggregations   the six *MV functions above, FILTER lanes included. Each segment gets, at the first query that
+ *                  needs them, raw single-value twins of the per-doc count / sum / min / max ("<col>$mvcount",
+ *                  "$mvsum" (LONG, exact, when max values x the dictionary's largest magnitude fits int64 in every
+ *                  segment of the batch; else "$mvsumd", DOUBLE, summed in value order), "$mvmin", "$mvmax"), which
+ *                  count in pinot_amd_segment_device_bytes; the query then aggregates those columns.
+ *   fetch          h_values the final double; h_values_i64 the exact COUNTMV and the integer SUMMV when it fits
+ *   fetch_intermediate   AVGMV: (sum, value count); MINMAXRANGEMV: (min, max); the others (final, 0)
+ * From pinot_amd_execute, naming the column: EUNSUPPORTED for an SV aggregation (SUMLONG, expressions, DISTINCTCOUNT,
+ * PERCENTILE, DISTINCTSUM, DISTINCTAVG included) or a key transform over an MV column, an *MV function over an SV
+ * column, GROUP BY an MV column, an MV column selected or ordered by in a selection query, and
+ * pinot_amd_query_set_group_key_values on an MV column; EINVAL for an *MV function over a STRING column and for a
+ * column that is MV in some segments of the batch and SV in others. */
+int pinot_amd_segment_add_mv_column(pinot_amd_segment* seg, const pinot_amd_column_spec* spec, int64_t total_num_values,
+                                    int32_t max_num_values_per_doc);
+/* 1 for a multi-value column (filling totalNumberOfEntries / maxNumberOfMultiValues; either may be NULL), 0 for a
+ * single-value column, < 0 on error. */
+int pinot_amd_segment_column_mv_info(const pinot_amd_segment* seg, const char* column, int64_t* total_values,
+                                     int32_t* max_values);
 int pinot_amd_segment_destroy(pinot_amd_segment* seg);
 int64_t pinot_amd_segment_num_docs(const pinot_amd_segment* seg);
 /* HBM bytes held by the segment (forward indexes + dictionaries + inverted indexes + directories). */
 int64_t pinot_amd_segment_device_bytes(const pinot_amd_segment* seg);
 /* Device pointer to a staged column's forward-index values (fixed-bit stream, raw values at
- * rawDataStart, or sorted pairs) — for the low-level entry points below. */
+ * rawDataStart, or sorted pairs; a multi-value column: its whole forward index file) — for the low-level entry
+ * points below. */
 const void* pinot_amd_segment_column_fwd(const pinot_amd_segment* seg, const char* column);
 /* The packed twin staging built for a raw INT / LONG column (value - base bit-packed in two planes; the
  * streaming scan kernels read it instead of the raw bytes, PINOT_AMD_PACKED=0 builds none). Returns 1 and fills
@@ -152,6 +204,13 @@ int pinot_amd_segment_column_packed_info(const pinot_amd_segment* seg, const cha
  * d_packed: big-endian MSB-first bit stream; writes length int32 dictIds to d_out. */
 int pinot_amd_fwd_read_dict_ids(const void* d_packed, int32_t bits, int64_t start_doc, int64_t length,
                                 int32_t* d_out, void* stream);
+
+/* FixedBitMVForwardIndexReader.getDictIdMV for the whole column (FixedBitMVForwardIndexReader.java:66-141): d_fwd is
+ * the MV forward index file in device memory (4-byte aligned, pinot_amd_required_padding() bytes of slack behind it;
+ * pinot_amd_segment_column_fwd of a staged MV column is one). Writes d_offsets[num_docs + 1] (doc d's values are
+ * [d_offsets[d], d_offsets[d + 1])) and the num_values dictIds in value order; either output may be NULL. */
+int pinot_amd_fwd_read_dict_ids_mv(const void* d_fwd, int64_t num_docs, int64_t num_values, int32_t bits,
+                                   int32_t* d_offsets, int32_t* d_dict_ids, void* stream);
 
 /* FixedBitSVForwardIndexWriter (local/io/writer/impl/FixedBitSVForwardIndexWriter.java) — packs
  * num_values int32 dictIds into the big-endian bit stream (ceil(n*bits/8) bytes written). */
@@ -262,7 +321,8 @@ int pinot_amd_query_add_group_by_transform(pinot_amd_query* q, const char* colum
                                            const pinot_amd_key_transform_spec* spec);
 /* Aggregation function (column NULL or "*" for COUNT(*)). Returns the aggregation index via out_index.
  * PINOT_AMD_AGG_DISTINCTCOUNT takes a column of any stored type, STRING included (EINVAL for NULL / "*").
- * Types above PINOT_AMD_AGG_DISTINCTCOUNT: EINVAL (pinot_amd_query_add_aggregation_param adds them). */
+ * Types above PINOT_AMD_AGG_DISTINCTCOUNT: EINVAL (pinot_amd_query_add_aggregation_param adds the value-set
+ * functions, pinot_amd_query_add_aggregation_mv the *MV functions). */
 int pinot_amd_query_add_aggregation(pinot_amd_query* q, int32_t agg_type, const char* column, int32_t* out_index);
 /* The same for every aggregation type, with the function's literal argument: `param` is the percentile of
  * PINOT_AMD_AGG_PERCENTILE, 0 <= param <= 100 (anything else, NaN included: EINVAL;
@@ -271,6 +331,11 @@ int pinot_amd_query_add_aggregation(pinot_amd_query* q, int32_t agg_type, const 
  * percentile is part of no cached plan's identity: queries that differ only in it run the same plans. */
 int pinot_amd_query_add_aggregation_param(pinot_amd_query* q, int32_t agg_type, const char* column, double param,
                                           int32_t* out_index);
+/* A multi-value aggregation, PINOT_AMD_AGG_COUNTMV .. PINOT_AMD_AGG_MINMAXRANGEMV, over one multi-value column (EINVAL
+ * for another type and for NULL / "*"). The two entry points above keep refusing every type beyond the ones they took
+ * before (EINVAL), so the *MV functions have their own. The aggregation may carry FILTER lanes
+ * (pinot_amd_query_add_aggregation_filter_predicate) like its single-value counterpart. */
+int pinot_amd_query_add_aggregation_mv(pinot_amd_query* q, int32_t agg_type, const char* column, int32_t* out_index);
 /* Aggregation over a binary arithmetic transform of two columns (SUM / MIN / MAX / AVG):
  * MultiplicationTransformFunction (times), SubtractionTransformFunction (minus),
  * AdditionTransformFunction (plus) in core/operator/transform/function/. Pinot evaluates these in
@@ -557,7 +622,8 @@ const char* pinot_amd_result_kernel_info(pinot_amd_result* r);
  * gate only the rows that pass it; selection-vector plans: the filter columns of every doc, 16 B per
  * vector entry (written + read) and the gathered columns of the matches; plus, per inverted-index leaf,
  * the selected bitmaps' serialized bytes and -- only when the expansion writes one -- the dense docId
- * bitset written and read once (the fused -fwselect plan writes none). */
+ * bitset written and read once (the fused -fwselect plan writes none); plus, per leaf on a multi-value column, its
+ * total_values * (bits + 1) / 8 bytes of dictIds and start bits and the dense docId bitset written and read once. */
 int pinot_amd_result_algorithmic_bytes(pinot_amd_result* r, double* h_bytes);
 /* Which raw columns the plan's streaming kernels read through their packed twins: "column:lo+hi" (plane bits
  * per doc) per column and shape launch, launches separated by ";", "" when none. Such columns count in

@@ -66,6 +66,8 @@ SIGNATURES = {
     "pinot_amd_jit_selftest": (C.c_int, [C.c_int]),
     "pinot_amd_segment_create": (C.c_int, [C.c_char_p, C.c_int64, _PP]),
     "pinot_amd_segment_add_column": (C.c_int, [_P, C.POINTER(ColumnSpec)]),
+    "pinot_amd_segment_add_mv_column": (C.c_int, [_P, C.POINTER(ColumnSpec), C.c_int64, C.c_int32]),
+    "pinot_amd_segment_column_mv_info": (C.c_int, [_P, C.c_char_p, _I64P, C.POINTER(C.c_int32)]),
     "pinot_amd_segment_destroy": (C.c_int, [_P]),
     "pinot_amd_segment_num_docs": (C.c_int64, [_P]),
     "pinot_amd_segment_device_bytes": (C.c_int64, [_P]),
@@ -73,6 +75,7 @@ SIGNATURES = {
     "pinot_amd_segment_column_packed_info": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pinot_amd_fwd_read_dict_ids": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, _P]),
+    "pinot_amd_fwd_read_dict_ids_mv": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P]),
     "pinot_amd_fwd_pack_dict_ids": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P]),
     "pinot_amd_fwd_read_raw": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _P, _P]),
     "pinot_amd_bitset_and": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
@@ -88,6 +91,7 @@ SIGNATURES = {
     "pinot_amd_query_add_aggregation": (C.c_int, [_P, C.c_int32, C.c_char_p, C.POINTER(C.c_int32)]),
     "pinot_amd_query_add_aggregation_param": (C.c_int, [_P, C.c_int32, C.c_char_p, C.c_double,
                                                         C.POINTER(C.c_int32)]),
+    "pinot_amd_query_add_aggregation_mv": (C.c_int, [_P, C.c_int32, C.c_char_p, C.POINTER(C.c_int32)]),
     "pinot_amd_query_set_num_groups_limit": (C.c_int, [_P, C.c_int64]),
     "pinot_amd_query_set_group_key_values": (C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int64, _I64P,
                                                        C.POINTER(C.c_double), C.POINTER(C.c_char_p)]),

@@ -384,4 +384,342 @@ hipError_t sort_rows_by_key(const uint64_t* keys, int nwk, const int* word_bits,
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// Multi-value columns (FixedBitMVForwardIndexReader's format, DevMvColumn): value-parallel over tiles of
+// kMvTileValues values. A value's doc is tile_first_doc[tile] + (start bits of the tile up to and including the
+// value) - 1: the tile's 128 bitmap dwords are staged in LDS with the exclusive prefix of their popcounts, a value
+// before the tile's first start bit belongs to the doc straddling in from the previous tile.
+//   mv_tile_count_kernel / mv_tile_scan_kernel   staging: start bits per tile, scanned into tile_first_doc
+//   mv_validate_kernel                           staging: bit 0, the chunk offset header, the longest doc
+//   mv_read_kernel                               getDictIdMV for the whole column (offsets and dictIds)
+//   mv_match_kernel                              an ANY-match predicate -> the segment's dense docId bitset
+//   mv_reduce_kernel                             per-doc count / sum / min / max (the *MV aggregations' twins)
+// ------------------------------------------------------------------------------------------------
+constexpr int kMvBmWords = kMvTileValues / 32;       // bitmap dwords of a tile
+constexpr int kMvPerThread = kMvTileValues / kBlock;  // values per lane
+constexpr int kMvWinWords = kMvTileValues / 32 + 4;   // 32-doc words a tile's docs (<= 4097) can touch
+static_assert(kMvBmWords == 128 && kBlock == 256, "the block's first two waves stage a tile's bitmap");
+
+__device__ __forceinline__ uint32_t mv_dict_id(const DevMvColumn& c, int64_t v) {
+  const int64_t b = c.raw_bit0 + v * c.bits;
+  const uint32_t* w = c.words + (b >> 5);
+  const uint64_t win = ((uint64_t)__builtin_bswap32(w[0]) << 32) | (uint64_t)__builtin_bswap32(w[1]);
+  return (uint32_t)((win << (uint32_t)(b & 31)) >> (64 - c.bits));
+}
+// bitmap dword j of the column (MSB = value 32 j), the bits at and beyond num_values cleared
+__device__ __forceinline__ uint32_t mv_bitmap_word(const DevMvColumn& c, int64_t j) {
+  const int64_t v0 = j * 32;
+  if (v0 >= c.num_values) return 0u;
+  uint32_t x = __builtin_bswap32(c.words[c.bm_word0 + j]);
+  const int64_t rem = c.num_values - v0;
+  if (rem < 32) x &= ~0u << (32 - (int)rem);
+  return x;
+}
+// Stages the tile's bitmap in bm[kMvBmWords] with pre[j] = start bits of the tile before dword j; returns the
+// tile's start bits. Every thread of the block calls it; the arrays are ready when it returns.
+__device__ __forceinline__ uint32_t mv_stage_tile(const DevMvColumn& c, int64_t tile, uint32_t* bm, uint32_t* pre,
+                                                  uint32_t* tot) {
+  const int tid = (int)threadIdx.x;
+  const uint32_t x = tid < kMvBmWords ? mv_bitmap_word(c, tile * kMvBmWords + tid) : 0u;
+  const uint32_t p = (uint32_t)__popc(x);
+  uint32_t inc = p;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t t = __shfl_up(inc, o, 64);
+    if ((tid & 63) >= o) inc += t;
+  }
+  if (tid == 63) tot[0] = inc;
+  __syncthreads();
+  if (tid < kMvBmWords) {
+    bm[tid] = x;
+    const uint32_t e = inc - p + (tid >= 64 ? tot[0] : 0u);
+    pre[tid] = e;
+    if (tid == kMvBmWords - 1) tot[1] = e + p;
+  }
+  __syncthreads();
+  return tot[1];
+}
+// start bits of the tile up to and including its value vi (0 .. kMvTileValues)
+__device__ __forceinline__ uint32_t mv_rank(const uint32_t* bm, const uint32_t* pre, int vi) {
+  return pre[vi >> 5] + (uint32_t)__popc(bm[vi >> 5] >> (31 - (vi & 31)));
+}
+
+__global__ void __launch_bounds__(kBlock) mv_tile_count_kernel(DevMvColumn c, int64_t ntiles, int32_t* counts) {
+  __shared__ uint32_t bm[kMvBmWords], pre[kMvBmWords], tot[2];
+  const int64_t tile = blockIdx.x;
+  if (tile >= ntiles) return;
+  const uint32_t n = mv_stage_tile(c, tile, bm, pre, tot);
+  if (threadIdx.x == 0) counts[tile] = (int32_t)n;
+}
+
+// exclusive scan of the tiles' counts in place (one block), total[0] = every start bit
+__global__ void __launch_bounds__(kBlock) mv_tile_scan_kernel(int32_t* counts, int64_t ntiles, long long* total) {
+  __shared__ long long wsum[kBlock / 64];
+  __shared__ long long carry;
+  const int tid = (int)threadIdx.x;
+  if (tid == 0) carry = 0;
+  __syncthreads();
+  for (int64_t base = 0; base < ntiles; base += kBlock) {
+    const int64_t i = base + tid;
+    const long long x = i < ntiles ? (long long)counts[i] : 0;
+    long long inc = x;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const long long t = __shfl_up(inc, o, 64);
+      if ((tid & 63) >= o) inc += t;
+    }
+    if ((tid & 63) == 63) wsum[tid >> 6] = inc;
+    __syncthreads();
+    long long before = carry;
+    for (int w = 0; w < (tid >> 6); ++w) before += wsum[w];
+    // (a rank beyond int32 cannot be a docId: the host refuses the column from the total)
+    if (i < ntiles) counts[i] = (int32_t)min(before + inc - x, (long long)INT32_MAX);
+    __syncthreads();
+    if (tid == kBlock - 1) carry = before + inc;
+    __syncthreads();
+  }
+  if (tid == 0) total[0] = carry;
+}
+
+// flags: 1 = bit 0 unset, 4 = a chunk offset header entry disagrees with the bitmap's rank, 8 = a doc longer
+// than max_values. header: the num_chunks big-endian entries at the head of the file.
+__global__ void __launch_bounds__(kBlock) mv_validate_kernel(DevMvColumn c, int64_t ntiles, int32_t docs_per_chunk,
+                                                             int32_t num_chunks, int32_t max_values, uint32_t* flags) {
+  __shared__ uint32_t bm[kMvBmWords], pre[kMvBmWords], tot[2];
+  const int64_t tile = blockIdx.x;
+  if (tile >= ntiles) return;
+  mv_stage_tile(c, tile, bm, pre, tot);
+  const int64_t tfd = c.tile_first_doc[tile];
+  const int tid = (int)threadIdx.x;
+  if (tile == 0 && tid == 0 && !(bm[0] >> 31)) atomicOr(flags, 1u);
+  uint32_t bad = 0;
+  if (tid < kMvBmWords) {
+    uint32_t x = bm[tid];
+    while (x) {
+      const int b = __clz((int)x);  // position from the MSB = value 32 tid + b of the tile
+      x &= ~(0x80000000u >> b);
+      const int vi = tid * 32 + b;
+      const int64_t v = tile * kMvTileValues + vi;
+      const int64_t d = tfd + (int64_t)mv_rank(bm, pre, vi) - 1;
+      if (docs_per_chunk > 0 && d % docs_per_chunk == 0) {
+        const int64_t k = d / docs_per_chunk;
+        if (k >= num_chunks || (int64_t)(int32_t)__builtin_bswap32(c.words[k]) != v) bad |= 4u;
+      }
+      // the doc's end: the next start bit (in this dword, or the first non-empty dword behind it) or num_values
+      int64_t end;
+      if (x) {
+        end = tile * kMvTileValues + tid * 32 + __clz((int)x);
+      } else {
+        const int64_t nwords = (c.num_values + 31) / 32;
+        // (a valid doc ends within max_values: the walk stops there)
+        const int64_t stop = min(nwords, (v + (int64_t)max_values) / 32 + 2);
+        end = stop < nwords ? (int64_t)1 << 62 : c.num_values;  // no start bit within reach: too long / the last doc
+        for (int64_t j = tile * kMvBmWords + tid + 1; j < stop; ++j) {
+          const uint32_t y = mv_bitmap_word(c, j);
+          if (y) {
+            end = j * 32 + __clz((int)y);
+            break;
+          }
+        }
+      }
+      if (end - v > (int64_t)max_values) bad |= 8u;
+    }
+  }
+  if (bad) atomicOr(flags, bad);
+}
+
+__global__ void __launch_bounds__(kBlock) mv_read_kernel(DevMvColumn c, int64_t ntiles, int32_t* offsets, int32_t* ids) {
+  __shared__ uint32_t bm[kMvBmWords], pre[kMvBmWords], tot[2];
+  const int64_t tile = blockIdx.x;
+  if (tile >= ntiles) return;
+  mv_stage_tile(c, tile, bm, pre, tot);
+  const int64_t tfd = c.tile_first_doc[tile];
+  if (tile == 0 && threadIdx.x == 0 && offsets) offsets[c.num_docs] = (int32_t)c.num_values;
+#pragma unroll 4
+  for (int j = 0; j < kMvPerThread; ++j) {
+    const int vi = j * kBlock + (int)threadIdx.x;
+    const int64_t v = tile * kMvTileValues + vi;
+    if (v >= c.num_values) break;
+    if (ids) ids[v] = (int32_t)mv_dict_id(c, v);
+    if (offsets && ((bm[vi >> 5] >> (31 - (vi & 31))) & 1u)) {
+      const int64_t d = tfd + (int64_t)mv_rank(bm, pre, vi) - 1;
+      if (d >= 0 && d < c.num_docs) offsets[d] = (int32_t)v;
+    }
+  }
+}
+
+// the predicate's dictId set (DevMvSet): a dictId range, the 64-bit accept mask, or a bitmap staged in LDS once per
+// block (read from HBM when it does not fit)
+__global__ void __launch_bounds__(kBlock) mv_match_kernel(DevMvColumn c, DevMvSet s, int64_t ntiles, uint32_t* bitset) {
+  extern __shared__ uint32_t lset[];
+  __shared__ uint32_t bm[kMvBmWords], pre[kMvBmWords], tot[2], win[kMvWinWords];
+  const int64_t tile = blockIdx.x;
+  if (tile >= ntiles) return;
+  const int tid = (int)threadIdx.x;
+  if (s.mode == MV_SET_LDS)
+    for (int i = tid; i < s.set_words; i += kBlock) lset[i] = s.set[i];
+  for (int i = tid; i < kMvWinWords; i += kBlock) win[i] = 0u;
+  mv_stage_tile(c, tile, bm, pre, tot);  // (its barriers also publish lset and win)
+  const int64_t tfd = c.tile_first_doc[tile];
+  // the tile's first doc: the straddling one unless the tile's first value starts a doc
+  const int64_t dmin = max(tfd - 1 + (int64_t)(bm[0] >> 31), (int64_t)0);
+  const int64_t wbase = dmin >> 5;
+  const uint64_t accept = s.accept;
+#pragma unroll 4
+  for (int j = 0; j < kMvPerThread; ++j) {
+    const int vi = j * kBlock + tid;
+    const int64_t v = tile * kMvTileValues + vi;
+    if (v >= c.num_values) break;
+    const uint32_t id = mv_dict_id(c, v);
+    bool hit;
+    switch (s.mode) {
+      case MV_SET_RANGE: hit = (int64_t)id >= s.lo && (int64_t)id < s.hi; break;
+      case MV_SET_ACCEPT: hit = id < 64u && ((accept >> id) & 1ull); break;
+      case MV_SET_LDS: hit = (int64_t)id < s.card && ((lset[id >> 5] >> (id & 31)) & 1u); break;
+      default: hit = (int64_t)id < s.card && ((s.set[id >> 5] >> (id & 31)) & 1u); break;
+    }
+    if (!hit) continue;
+    const int64_t d = tfd + (int64_t)mv_rank(bm, pre, vi) - 1;
+    const int64_t w = (d >> 5) - wbase;
+    if (d >= dmin && d < c.num_docs && w < kMvWinWords) atomicOr(&win[w], 1u << (d & 31));
+  }
+  __syncthreads();
+  // boundary words are shared with the neighbouring tiles: OR, never store
+  for (int i = tid; i < kMvWinWords; i += kBlock)
+    if (win[i]) atomicOr(&bitset[wbase + i], win[i]);
+}
+
+__device__ __forceinline__ uint64_t mv_value_bits(const void* dict, int type, uint32_t id, bool as_double) {
+  if (type == T_INT || type == T_LONG) {
+    const int64_t x = type == T_INT ? (int64_t)reinterpret_cast<const int32_t*>(dict)[id]
+                                    : reinterpret_cast<const int64_t*>(dict)[id];
+    return as_double ? (uint64_t)__double_as_longlong((double)x) : (uint64_t)x;
+  }
+  const double x = type == T_FLOAT ? (double)reinterpret_cast<const float*>(dict)[id]
+                                   : reinterpret_cast<const double*>(dict)[id];
+  return (uint64_t)__double_as_longlong(x);
+}
+
+// One word per doc in out[num_docs], initialised by the host to the op's identity (0, MV_RED_MIN: ~0):
+//   MV_RED_COUNT    the doc's values
+//   MV_RED_SUM_I64  their exact (wrapping) int64 sum; INT / LONG columns
+//   MV_RED_SUM_F64  the bits of their double sum, added in value order by the lane of the doc's first value
+//   MV_RED_MIN/MAX  the order-preserving key of the least / greatest value (INT / LONG: value ^ 2^63, FLOAT / DOUBLE:
+//                   Double.compare's key, NaN values skipped), the identity when no value entered
+// A segmented reduction keyed by doc-in-tile in LDS; the tile's first and last doc may straddle into the
+// neighbouring tiles and are flushed with global atomics, the docs between them stored.
+__global__ void __launch_bounds__(kBlock) mv_reduce_kernel(DevMvColumn c, const void* dict, int type, int op,
+                                                           int64_t ntiles, unsigned long long* out) {
+  __shared__ uint32_t bm[kMvBmWords], pre[kMvBmWords], tot[2];
+  __shared__ unsigned long long acc[kMvTileValues + 1];
+  const int64_t tile = blockIdx.x;
+  if (tile >= ntiles) return;
+  const int tid = (int)threadIdx.x;
+  const unsigned long long ident = op == MV_RED_MIN ? ~0ull : 0ull;
+  for (int i = tid; i < kMvTileValues + 1; i += kBlock) acc[i] = ident;
+  const uint32_t nstart = mv_stage_tile(c, tile, bm, pre, tot);
+  const int64_t tfd = c.tile_first_doc[tile];
+  const int64_t lead = 1 - (int64_t)(bm[0] >> 31);  // 1: the tile begins inside the straddling doc
+  const int64_t dmin = tfd - lead;
+  const int ndocs = (int)nstart + (int)lead;
+  const bool fl = type == T_FLOAT || type == T_DOUBLE;
+#pragma unroll 2
+  for (int j = 0; j < kMvPerThread; ++j) {
+    const int vi = j * kBlock + tid;
+    const int64_t v = tile * kMvTileValues + vi;
+    if (v >= c.num_values) break;
+    const int64_t d = tfd + (int64_t)mv_rank(bm, pre, vi) - 1;
+    if (d < 0 || d >= c.num_docs) continue;
+    if (op == MV_RED_SUM_F64) {
+      if (!((bm[vi >> 5] >> (31 - (vi & 31))) & 1u)) continue;
+      double sum = 0.0;
+      int64_t u = v;
+      do {
+        sum += __longlong_as_double((long long)mv_value_bits(dict, type, mv_dict_id(c, u), true));
+        ++u;
+      } while (u < c.num_values && !((__builtin_bswap32(c.words[c.bm_word0 + (u >> 5)]) >> (31 - (int)(u & 31))) & 1u));
+      out[d] = (unsigned long long)__double_as_longlong(sum);
+      continue;
+    }
+    unsigned long long* a = &acc[d - dmin];
+    if (op == MV_RED_COUNT) {
+      atomicAdd(a, 1ull);
+      continue;
+    }
+    const uint64_t bits = mv_value_bits(dict, type, mv_dict_id(c, v), false);
+    if (op == MV_RED_SUM_I64) {
+      atomicAdd(a, (unsigned long long)bits);
+      continue;
+    }
+    uint64_t key;
+    if (fl) {
+      const double x = __longlong_as_double((long long)bits);
+      if (x != x) continue;  // value < min / value > max: NaN never enters
+      key = java_double_order_dev(x);
+    } else {
+      key = bits ^ (1ull << 63);
+    }
+    if (op == MV_RED_MIN) atomicMin(a, (unsigned long long)key);
+    else atomicMax(a, (unsigned long long)key);
+  }
+  if (op == MV_RED_SUM_F64) return;
+  __syncthreads();
+  for (int i = tid; i < ndocs; i += kBlock) {
+    const unsigned long long x = acc[i];
+    const int64_t d = dmin + i;
+    if (d < 0 || d >= c.num_docs) continue;
+    if (i > 0 && i < ndocs - 1) {
+      out[d] = x;
+    } else if (x != ident) {
+      if (op == MV_RED_MIN) atomicMin(&out[d], x);
+      else if (op == MV_RED_MAX) atomicMax(&out[d], x);
+      else atomicAdd(&out[d], x);
+    }
+  }
+}
+
+__global__ void fill_u64_kernel(unsigned long long* p, int64_t n, unsigned long long x) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = x;
+}
+
+int64_t mv_num_tiles(int64_t num_values) { return (num_values + kMvTileValues - 1) / kMvTileValues; }
+
+hipError_t launch_mv_index(const DevMvColumn& c, int32_t* tile_first_doc, long long* total, hipStream_t st) {
+  const int64_t nt = mv_num_tiles(c.num_values);
+  if (nt > 0) hipLaunchKernelGGL(mv_tile_count_kernel, dim3((unsigned)nt), dim3(kBlock), 0, st, c, nt, tile_first_doc);
+  hipLaunchKernelGGL(mv_tile_scan_kernel, dim3(1), dim3(kBlock), 0, st, tile_first_doc, nt, total);
+  return hipGetLastError();
+}
+hipError_t launch_mv_validate(const DevMvColumn& c, int32_t docs_per_chunk, int32_t num_chunks, int32_t max_values,
+                              uint32_t* flags, hipStream_t st) {
+  const int64_t nt = mv_num_tiles(c.num_values);
+  if (nt <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mv_validate_kernel, dim3((unsigned)nt), dim3(kBlock), 0, st, c, nt, docs_per_chunk, num_chunks,
+                     max_values, flags);
+  return hipGetLastError();
+}
+hipError_t launch_mv_read(const DevMvColumn& c, int32_t* offsets, int32_t* ids, hipStream_t st) {
+  const int64_t nt = mv_num_tiles(c.num_values);
+  if (nt <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mv_read_kernel, dim3((unsigned)nt), dim3(kBlock), 0, st, c, nt, offsets, ids);
+  return hipGetLastError();
+}
+hipError_t launch_mv_match(const DevMvColumn& c, const DevMvSet& s, uint32_t* bitset, hipStream_t st) {
+  const int64_t nt = mv_num_tiles(c.num_values);
+  if (nt <= 0) return hipSuccess;
+  const size_t lds = s.mode == MV_SET_LDS ? (size_t)s.set_words * 4 : 0;
+  hipLaunchKernelGGL(mv_match_kernel, dim3((unsigned)nt), dim3(kBlock), lds, st, c, s, nt, bitset);
+  return hipGetLastError();
+}
+hipError_t launch_mv_reduce(const DevMvColumn& c, const void* dict, int type, int op, unsigned long long* out,
+                            hipStream_t st) {
+  const int64_t nt = mv_num_tiles(c.num_values);
+  if (c.num_docs > 0)
+    hipLaunchKernelGGL(fill_u64_kernel, dim3(grid_of(c.num_docs)), dim3(256), 0, st, out, c.num_docs,
+                       op == MV_RED_MIN ? ~0ull : 0ull);
+  if (nt <= 0) return hipGetLastError();
+  hipLaunchKernelGGL(mv_reduce_kernel, dim3((unsigned)nt), dim3(kBlock), 0, st, c, dict, type, op, nt, out);
+  return hipGetLastError();
+}
+
 }  // namespace pamd

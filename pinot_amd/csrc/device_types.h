@@ -21,7 +21,9 @@ constexpr int kValueScanBlocks = 1024;              // blocks of the value-set f
 constexpr int kPadBytes = 4 * kTileDocs * 8 + 256;
 
 // column encodings (pinot_amd_fwd_encoding)
-enum : int32_t { ENC_FIXED_BIT = 0, ENC_RAW = 1, ENC_SORTED = 2 };
+// (ENC_FIXED_BIT_MV: a multi-value column; no scan reads one -- its predicates arrive as LEAF_DOC_BITSET leaves, its
+// aggregations through single-value twins)
+enum : int32_t { ENC_FIXED_BIT = 0, ENC_RAW = 1, ENC_SORTED = 2, ENC_FIXED_BIT_MV = 3 };
 // value types (pinot_amd_data_type)
 enum : int32_t { T_INT = 0, T_LONG = 1, T_FLOAT = 2, T_DOUBLE = 3, T_STRING = 4 };
 

@@ -366,7 +366,47 @@ struct Column {
   std::vector<uint64_t> inv_bytes;  // serialized bitmap bytes of dictIds < d (prefix, card+1 entries)
   std::vector<uint16_t> inv_keys;   // container -> key (high 16 bits of its docIds)
   bool has_inv = false;
+  // multi-value column (ENC_FIXED_BIT_MV): `fwd` is the whole FixedBitMVForwardIndexWriter file (chunk offsets,
+  // start-bit bitmap, dictId stream); mv_tfd the rank of the first value of every kMvTileValues-value tile
+  bool mv = false;
+  int64_t mv_total = 0;
+  int32_t mv_max = 0;
+  int64_t mv_bm_off = 0, mv_raw_off = 0;  // byte offsets of the bitmap and of the dictId stream in the file
+  DevBuf mv_tfd;
 };
+
+// the device view of a staged MV column
+static DevMvColumn mv_dev(const Column& c, int64_t num_docs) {
+  DevMvColumn d{};
+  d.words = (const uint32_t*)c.fwd.p;
+  d.bm_word0 = c.mv_bm_off / 4;
+  d.raw_bit0 = c.mv_raw_off * 8;
+  d.num_values = c.mv_total;
+  d.num_docs = num_docs;
+  d.tile_first_doc = (const int32_t*)c.mv_tfd.p;
+  d.bits = c.bits;
+  return d;
+}
+
+// FixedBitMVForwardIndexWriter's layout for numDocs docs and totalNumValues values: byte offsets of the bitmap and
+// the dictId stream, the file's size; false when the counts cannot be a column's
+struct MvLayout {
+  int32_t docs_per_chunk = 0, num_chunks = 0;
+  int64_t bm_off = 0, raw_off = 0, size = 0;
+};
+static bool mv_layout(int64_t num_docs, int64_t total, int bits, MvLayout* L) {
+  *L = MvLayout();
+  if (num_docs < 0 || total < num_docs || total > (int64_t)std::numeric_limits<int32_t>::max() || bits < 1 || bits > 31)
+    return false;
+  if (num_docs == 0) return total == 0;
+  const float avg = (float)(total / num_docs);  // Java int division, then float
+  L->docs_per_chunk = (int32_t)std::ceil(2048.0f / avg);
+  L->num_chunks = (int32_t)((num_docs + L->docs_per_chunk - 1) / L->docs_per_chunk);
+  L->bm_off = 4 * (int64_t)L->num_chunks;
+  L->raw_off = L->bm_off + (total + 7) / 8;
+  L->size = L->raw_off + (total * bits + 7) / 8;
+  return true;
+}
 
 // A predicate leaf resolved on one segment (make_leaf_for_segment), kept on the segment: a re-issued filter
 // skips the dictionary lookups, the inverted-index container selection and the descriptor uploads (the
@@ -380,6 +420,8 @@ struct LeafCacheEntry {
   DevBuf *sel = nullptr, *grp = nullptr, *psel = nullptr;
   int32_t nsel = 0, nchunks = 0;
   double alg_bytes = 0, bitset_bytes = 0;
+  bool mv = false;  // multi-value leaf: a docId bitset per execution, matched against `mvset`
+  DevMvSet mvset{};
 };
 
 struct pinot_amd_segment {
@@ -928,6 +970,8 @@ int pinot_amd_segment_column_packed_info(const pinot_amd_segment* seg, const cha
 int pinot_amd_segment_add_column(pinot_amd_segment* seg, const pinot_amd_column_spec* spec) {
   if (!seg || !spec || !spec->name) return fail(PINOT_AMD_EINVAL, "add_column: bad arguments");
   if (seg->cols.count(spec->name)) return fail(PINOT_AMD_EINVAL, "add_column: duplicate column %s", spec->name);
+  if (spec->encoding == ENC_FIXED_BIT_MV)
+    return fail(PINOT_AMD_EINVAL, "column %s: a multi-value column is staged with pinot_amd_segment_add_mv_column", spec->name);
   ++seg->gen;
   if (spec->encoding == ENC_RAW && spec->stored_type == T_STRING) {
     // Raw STRING column: staged dictionary-encoded, as ForwardIndexHandler's ENABLE_DICTIONARY operation
@@ -1073,9 +1117,141 @@ int pinot_amd_segment_add_column(pinot_amd_segment* seg, const pinot_amd_column_
   return 0;
 }
 
+// tile_first_doc of an MV file in device memory and the checks of the staged bytes that need the device
+// (mv_tile_count_kernel / mv_tile_scan_kernel / mv_validate_kernel): *popcount the bitmap's set bits, *flags
+// mv_validate_kernel's (max_values <= 0: the index alone)
+static int mv_index(const DevMvColumn& view, const MvLayout& lay, int32_t max_values, DevBuf* tfd, int64_t* popcount,
+                    uint32_t* flags, hipStream_t st) {
+  const int64_t nt = mv_num_tiles(view.num_values);
+  if (int rc = tfd->alloc((size_t)std::max<int64_t>(nt, 1) * 4 + 64)) return rc;
+  HIP_OK(hipMemsetAsync(tfd->p, 0, tfd->n, st));
+  DevBuf out;
+  if (int rc = out.alloc(16)) return rc;
+  HIP_OK(hipMemsetAsync(out.p, 0, 16, st));
+  DevMvColumn v = view;
+  v.tile_first_doc = (const int32_t*)tfd->p;
+  HIP_OK(launch_mv_index(v, (int32_t*)tfd->p, (long long*)out.p, st));
+  if (max_values > 0)
+    HIP_OK(launch_mv_validate(v, lay.docs_per_chunk, lay.num_chunks, max_values, (uint32_t*)((uint8_t*)out.p + 8), st));
+  uint64_t h[2] = {0, 0};
+  HIP_OK(hipMemcpyAsync(h, out.p, 16, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  *popcount = (int64_t)h[0];
+  *flags = (uint32_t)h[1];
+  return 0;
+}
+
+int pinot_amd_segment_add_mv_column(pinot_amd_segment* seg, const pinot_amd_column_spec* spec, int64_t total_num_values,
+                                    int32_t max_num_values_per_doc) {
+  if (!seg || !spec || !spec->name) return fail(PINOT_AMD_EINVAL, "add_mv_column: bad arguments");
+  if (seg->cols.count(spec->name)) return fail(PINOT_AMD_EINVAL, "add_mv_column: duplicate column %s", spec->name);
+  if (spec->encoding != ENC_FIXED_BIT_MV)
+    return fail(PINOT_AMD_EINVAL, "column %s: add_mv_column takes PINOT_AMD_FWD_FIXED_BIT_MV (encoding %d)", spec->name,
+                spec->encoding);
+  if (spec->h_inverted && spec->inverted_size)
+    return fail(PINOT_AMD_EUNSUPPORTED, "column %s: inverted index on a multi-value column", spec->name);
+  auto c = std::make_unique<Column>();
+  c->name = spec->name;
+  c->type = spec->stored_type;
+  c->enc = ENC_FIXED_BIT_MV;
+  c->card = spec->cardinality;
+  c->bits = spec->bits_per_element;
+  c->mv = true;
+  c->mv_total = total_num_values;
+  c->mv_max = max_num_values_per_doc;
+  const int64_t nd = seg->num_docs;
+  if (c->type < T_INT || c->type > T_STRING) return fail(PINOT_AMD_EINVAL, "column %s: bad type", spec->name);
+  if (c->bits < 1 || c->bits > 31) return fail(PINOT_AMD_EINVAL, "column %s: bitsPerElement %d", spec->name, c->bits);
+  if (c->card < 0 || (nd > 0 && c->card < 1)) return fail(PINOT_AMD_EINVAL, "column %s: cardinality %d", spec->name, c->card);
+  MvLayout lay;
+  if (!mv_layout(nd, total_num_values, c->bits, &lay))
+    return fail(PINOT_AMD_EINVAL, "column %s: %lld values cannot fill %lld multi-value docs", spec->name,
+                (long long)total_num_values, (long long)nd);
+  if (nd > 0 && max_num_values_per_doc < 1)
+    return fail(PINOT_AMD_EINVAL, "column %s: maxNumberOfMultiValues %d", spec->name, max_num_values_per_doc);
+  if ((int64_t)spec->fwd_size != lay.size || (lay.size > 0 && !spec->h_fwd))
+    return fail(PINOT_AMD_EINVAL, "column %s: multi-value forward index of %zu bytes, %lld docs and %lld values at %d bits make %lld",
+                spec->name, spec->fwd_size, (long long)nd, (long long)total_num_values, c->bits, (long long)lay.size);
+  if (!spec->h_dictionary && !(c->card == 0 && spec->dictionary_size == 0))
+    return fail(PINOT_AMD_EINVAL, "column %s: dictionary required", spec->name);
+  c->mv_bm_off = lay.bm_off;
+  c->mv_raw_off = lay.raw_off;
+  if (int rc = c->fwd.alloc_copy(spec->h_fwd, (size_t)lay.size, kPadBytes)) return rc;
+  if (int rc = decode_dictionary(*c, (const uint8_t*)spec->h_dictionary, spec->dictionary_size)) return rc;
+  if (!c->dict_i.empty()) {
+    c->has_range = true;
+    c->vmin = c->dict_i.front();
+    c->vmax = c->dict_i.back();
+  }
+  int64_t pop = 0;
+  uint32_t flags = 0;
+  if (int rc = mv_index(mv_dev(*c, nd), lay, std::max(max_num_values_per_doc, 1), &c->mv_tfd, &pop, &flags, nullptr)) return rc;
+  if (pop != nd)
+    return fail(PINOT_AMD_EINVAL, "column %s: the bitmap marks %lld docs, the segment has %lld", spec->name, (long long)pop,
+                (long long)nd);
+  if (flags & 1u) return fail(PINOT_AMD_EINVAL, "column %s: value 0 does not start a doc", spec->name);
+  if (flags & 4u) return fail(PINOT_AMD_EINVAL, "column %s: a chunk offset disagrees with the bitmap", spec->name);
+  if (flags & 8u)
+    return fail(PINOT_AMD_EINVAL, "column %s: a doc holds more than maxNumberOfMultiValues = %d values", spec->name,
+                max_num_values_per_doc);
+  StagedPrint sp{c->fwd.n, 0};
+  if (int rc = device_fingerprint(c->fwd.p, sp.bytes, &sp.print)) return rc;
+  {
+    std::lock_guard<std::mutex> g(g_print_mu);
+    g_prints[c->fwd.p] = sp;
+  }
+  ++seg->gen;
+  seg->device_bytes += (int64_t)(c->fwd.n + c->dict.n + c->mv_tfd.n);
+  seg->cols[c->name] = std::move(c);
+  return 0;
+}
+
+int pinot_amd_segment_column_mv_info(const pinot_amd_segment* seg, const char* column, int64_t* total_values,
+                                     int32_t* max_values) {
+  if (!seg || !column) return fail(PINOT_AMD_EINVAL, "column_mv_info: bad arguments");
+  auto it = seg->cols.find(column);
+  if (it == seg->cols.end()) return fail(PINOT_AMD_EINVAL, "column_mv_info: no column %s", column);
+  const Column& c = *it->second;
+  if (!c.mv) return 0;
+  if (total_values) *total_values = c.mv_total;
+  if (max_values) *max_values = c.mv_max;
+  return 1;
+}
+
 // ------------------------------------------------------------------------------------------------
 // low-level operators
 // ------------------------------------------------------------------------------------------------
+int pinot_amd_fwd_read_dict_ids_mv(const void* d_fwd, int64_t num_docs, int64_t num_values, int32_t bits,
+                                   int32_t* d_offsets, int32_t* d_dict_ids, void* stream) {
+  MvLayout lay;
+  if (!d_fwd || ((uintptr_t)d_fwd & 3) || !mv_layout(num_docs, num_values, bits, &lay))
+    return fail(PINOT_AMD_EINVAL, "fwd_read_dict_ids_mv: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  if (num_docs == 0) {
+    if (d_offsets) HIP_OK(hipMemsetAsync(d_offsets, 0, 4, st));
+    return 0;
+  }
+  if (!d_offsets && !d_dict_ids) return 0;
+  DevMvColumn v{};
+  v.words = (const uint32_t*)d_fwd;
+  v.bm_word0 = lay.bm_off / 4;
+  v.raw_bit0 = lay.raw_off * 8;
+  v.num_values = num_values;
+  v.num_docs = num_docs;
+  v.bits = bits;
+  DevBuf tfd;
+  int64_t pop = 0;
+  uint32_t flags = 0;
+  if (int rc = mv_index(v, lay, 0, &tfd, &pop, &flags, st)) return rc;
+  if (pop != num_docs)
+    return fail(PINOT_AMD_EINVAL, "fwd_read_dict_ids_mv: the bitmap marks %lld docs, not %lld", (long long)pop,
+                (long long)num_docs);
+  v.tile_first_doc = (const int32_t*)tfd.p;
+  HIP_OK(launch_mv_read(v, d_offsets, d_dict_ids, st));
+  HIP_OK(hipStreamSynchronize(st));  // (tile_first_doc is released on return)
+  return 0;
+}
+
 int pinot_amd_fwd_read_dict_ids(const void* d_packed, int32_t bits, int64_t start_doc, int64_t length, int32_t* d_out,
                                 void* stream) {
   if (!d_packed || !d_out || bits < 1 || bits > 31 || start_doc < 0 || length < 0)
@@ -1214,6 +1390,9 @@ struct AggSpec {
 // the aggregations answered from a value-set query (execute_distinct): DISTINCTCOUNT, PERCENTILE, DISTINCTSUM,
 // DISTINCTAVG
 static bool is_value_set_agg(int32_t t) { return t >= PINOT_AMD_AGG_DISTINCTCOUNT && t <= PINOT_AMD_AGG_DISTINCTAVG; }
+// the multi-value aggregations: planned over the single-value twins of the column's per-doc count / sum / min / max
+// (PlanBuild::raw_keys redirects AggSpec::column, and column2 for the two that read a second twin)
+static bool is_mv_agg(int32_t t) { return t >= PINOT_AMD_AGG_COUNTMV && t <= PINOT_AMD_AGG_MINMAXRANGEMV; }
 
 struct MergedKeyColumn {
   int32_t type = 0;
@@ -1431,6 +1610,9 @@ int pinot_amd_query_add_aggregation(pinot_amd_query* q, int32_t agg_type, const 
 int pinot_amd_query_add_aggregation_param(pinot_amd_query* q, int32_t agg_type, const char* column, double param,
                                           int32_t* out_index) {
   if (!q) return fail(PINOT_AMD_EINVAL, "add_aggregation_param: null query");
+  if (is_mv_agg(agg_type))
+    return fail(PINOT_AMD_EINVAL, "add_aggregation_param: a multi-value aggregation is added with "
+                                  "pinot_amd_query_add_aggregation_mv");
   if (agg_type < PINOT_AMD_AGG_COUNT || agg_type > PINOT_AMD_AGG_DISTINCTAVG)
     return fail(PINOT_AMD_EINVAL, "add_aggregation_param: bad type");
   // AggregationFunctionFactory.java:534-536: 0 <= percentile <= 100 (NaN fails both comparisons)
@@ -1442,6 +1624,16 @@ int pinot_amd_query_add_aggregation_param(pinot_amd_query* q, int32_t agg_type, 
     return fail(PINOT_AMD_EINVAL, "add_aggregation_param: column required");
   if (out_index) *out_index = (int32_t)q->aggs.size();
   q->aggs.push_back(a);
+  return 0;
+}
+
+int pinot_amd_query_add_aggregation_mv(pinot_amd_query* q, int32_t agg_type, const char* column, int32_t* out_index) {
+  if (!q) return fail(PINOT_AMD_EINVAL, "add_aggregation_mv: null query");
+  if (!is_mv_agg(agg_type)) return fail(PINOT_AMD_EINVAL, "add_aggregation_mv: %d is no multi-value aggregation", agg_type);
+  if (!column || !*column || strcmp(column, "*") == 0)
+    return fail(PINOT_AMD_EINVAL, "add_aggregation_mv: column required");
+  if (out_index) *out_index = (int32_t)q->aggs.size();
+  q->aggs.push_back(AggSpec{agg_type, column});
   return 0;
 }
 
@@ -1690,7 +1882,19 @@ struct pinot_amd_result {
     DevBuf* psel = nullptr;  // packed descriptors in sel order (ExpandJob::psel), or none
   };
   std::vector<InvLeaf> inv_leaves;
-  DevBuf d_expand_jobs;        // one ExpandJob per inv_leaves entry (batched clear + expand launches)
+  // multi-value leaves to (re)build each execution: the docs with any value in the leaf's dictId set, ORed into a
+  // zeroed dense docId bitset (mv_match_kernel) where the inverted-index expansion runs
+  struct MvLeaf {
+    int seg;
+    const Column* col;
+    DevBuf* bitset;
+    DevMvSet set;
+    int64_t num_docs;
+    double alg_bytes;     // the dictId stream and the start-bit bitmap, read once
+    double bitset_bytes;  // the dense docId bitset written and read once
+  };
+  std::vector<MvLeaf> mv_leaves;
+  DevBuf d_expand_jobs;       // one ExpandJob per inv_leaves entry (batched clear + expand launches)
   int64_t expand_total = 0;   // work items: (job, 65536-doc chunk) pairs
   std::vector<std::unique_ptr<DevBuf>> bitsets;  // filter-only plans: one docId bitset per segment
   std::vector<int64_t> bitset_words;
@@ -2240,6 +2444,43 @@ static int make_leaf_uncached(pinot_amd_result* r, int si, const pinot_amd_segme
     L->slot = -1;
     return 0;
   }
+  if (c.mv) {
+    // BaseDictionaryBasedPredicateEvaluator.applyMV: a doc matches when any of its values is in the set; the
+    // exclusive predicates are this leaf negated (above), never ANY over the complement. (An empty set is alwaysFalse
+    // and a full one alwaysTrue, above: every doc has at least one value.) The docs are ORed into a dense docId bitset
+    // by mv_match_kernel inside each execution; the scan sees the inverted index's LEAF_DOC_BITSET.
+    DevMvSet S{};
+    S.card = c.card;
+    if (is_range) {
+      S.mode = MV_SET_RANGE;
+      S.lo = start;
+      S.hi = end;
+    } else if (c.card <= 64) {
+      S.mode = MV_SET_ACCEPT;
+      S.accept = L->accept;
+    } else {
+      std::vector<uint32_t> mask(((size_t)c.card + 31) / 32, 0u);
+      for (int32_t d : ids) mask[d >> 5] |= 1u << (d & 31);
+      auto buf = std::make_unique<DevBuf>();
+      if (int rc = buf->alloc_copy(mask.data(), mask.size() * 4, 64)) return rc;
+      S.set = (const uint32_t*)buf->p;
+      S.set_words = (int32_t)mask.size();
+      S.mode = mask.size() * 4 <= (size_t)32 * 1024 ? MV_SET_LDS : MV_SET_HBM;
+      r->owned.push_back(std::move(buf));
+    }
+    const int64_t tiles = (seg->num_docs + kTileDocs - 1) / kTileDocs;
+    const size_t bs_bytes = (size_t)std::max<int64_t>(tiles, 1) * kTileDocs / 8 + 64;
+    auto bs = std::make_unique<DevBuf>();
+    if (int rc = bs->alloc(bs_bytes + kBitsetSlackBytes)) return rc;  // (the slack: see the inverted-index leaf below)
+    r->mv_leaves.push_back({si, &c, bs.get(), S, seg->num_docs, (double)c.mv_total * (c.bits + 1) / 8.0,
+                            2.0 * (double)((seg->num_docs + 7) / 8)});
+    L->kind = LEAF_DOC_BITSET;
+    L->bits = (const uint32_t*)bs->p;
+    L->slot = -1;
+    *needs_slot = false;
+    r->owned.push_back(std::move(bs));
+    return 0;
+  }
   if (c.enc == ENC_SORTED && is_range) {
     // SortedIndexBasedFilterOperator: a dictId range of a sorted column is one docId range
     L->kind = LEAF_DOC_RANGE;
@@ -2359,9 +2600,16 @@ static int make_leaf_for_segment(pinot_amd_result* r, int si, pinot_amd_segment*
                                hit->alg_bytes, hit->bitset_bytes, hit->psel});
       r->owned.push_back(std::move(bs));
     }
+    if (hit->mv) {
+      auto bs = std::make_unique<DevBuf>();
+      if (int rc = bs->alloc(hit->bitset_alloc)) return rc;
+      L->bits = (const uint32_t*)bs->p;
+      r->mv_leaves.push_back({si, &c, bs.get(), hit->mvset, seg->num_docs, hit->alg_bytes, hit->bitset_bytes});
+      r->owned.push_back(std::move(bs));
+    }
     return 0;
   }
-  const size_t o0 = r->owned.size(), i0 = r->inv_leaves.size();
+  const size_t o0 = r->owned.size(), i0 = r->inv_leaves.size(), m0 = r->mv_leaves.size();
   if (int rc = make_leaf_uncached(r, si, seg, p, c, slot, L, needs_slot, st, decoded_anyway)) return rc;
   auto e = std::make_shared<LeafCacheEntry>();
   e->L = *L;
@@ -2380,6 +2628,15 @@ static int make_leaf_for_segment(pinot_amd_result* r, int si, pinot_amd_segment*
     e->bitset_bytes = il.bitset_bytes;
     bitset = il.bitset;
     HIP_OK(hipStreamSynchronize(st));  // the packed descriptors (launch_pack_sel) are read by later streams
+  }
+  if (r->mv_leaves.size() > m0) {
+    const auto& ml = r->mv_leaves.back();
+    e->mv = true;
+    e->bitset_alloc = ml.bitset->n;
+    e->mvset = ml.set;
+    e->alg_bytes = ml.alg_bytes;
+    e->bitset_bytes = ml.bitset_bytes;
+    bitset = ml.bitset;
   }
   // the leaf's descriptor buffers move to shared ownership (same objects: the pointers above stay valid);
   // the per-execution docId bitset stays owned by this result
@@ -2496,6 +2753,152 @@ static int derive_transform_twin(pinot_amd_segment* s, const std::string& col, c
     }
   }
   return stage_derived_twin(s, twin, T_LONG, nd, nd > 0 ? doc_ids : ids, dict_be, card);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Multi-value columns in a query
+// ------------------------------------------------------------------------------------------------
+// What a query may not do with a multi-value column, over the whole batch and before anything is built (a refusal
+// stages nothing). A column the segments do not have is left to the planner's own message.
+static int check_mv_query(const pinot_amd_query& Q, pinot_amd_segment* const* segs, int32_t n, bool filter_only) {
+  if (!segs || n < 1) return 0;
+  int rc = 0;
+  // 1: multi-value in every segment that has the column, 0: in none
+  auto mv_of = [&](const std::string& col) -> int {
+    int have = 0, mv = 0;
+    for (int32_t i = 0; i < n; ++i) {
+      if (!segs[i]) continue;
+      auto it = segs[i]->cols.find(col);
+      if (it == segs[i]->cols.end()) continue;
+      ++have;
+      mv += it->second->mv ? 1 : 0;
+    }
+    if (mv != 0 && mv != have && !rc)
+      rc = fail(PINOT_AMD_EINVAL, "column %s is multi-value in some segments of the batch and single-value in others",
+                col.c_str());
+    return mv != 0;
+  };
+  auto type_of = [&](const std::string& col) -> int {
+    for (int32_t i = 0; i < n; ++i) {
+      if (!segs[i]) continue;
+      auto it = segs[i]->cols.find(col);
+      if (it != segs[i]->cols.end()) return it->second->type;
+    }
+    return -1;
+  };
+  for (const PredSpec& p : Q.preds) (void)mv_of(p.column);
+  if (rc || filter_only) return rc;
+  for (const auto& f : Q.agg_filter)
+    for (const PredSpec& p : f) (void)mv_of(p.column);
+  if (rc) return rc;
+  for (const std::string& g : Q.group_by) {
+    auto kt = Q.key_tf.find(g);
+    const std::string& col = kt != Q.key_tf.end() ? kt->second.column : g;
+    if (mv_of(col) && !rc)
+      rc = fail(PINOT_AMD_EUNSUPPORTED, kt != Q.key_tf.end() ? "GROUP BY transform of multi-value column %s"
+                                                             : "GROUP BY on multi-value column %s", col.c_str());
+    if (rc) return rc;
+  }
+  for (const auto& ks : Q.key_space) {
+    if (mv_of(ks.first) && !rc)
+      rc = fail(PINOT_AMD_EUNSUPPORTED, "set_group_key_values on multi-value column %s", ks.first.c_str());
+    if (rc) return rc;
+  }
+  for (const std::string& c : Q.sel_cols) {
+    if (mv_of(c) && !rc) rc = fail(PINOT_AMD_EUNSUPPORTED, "selection of multi-value column %s", c.c_str());
+    if (rc) return rc;
+  }
+  for (const auto& o : Q.sel_order) {
+    if (mv_of(o.column) && !rc)
+      rc = fail(PINOT_AMD_EUNSUPPORTED, "selection ORDER BY multi-value column %s", o.column.c_str());
+    if (rc) return rc;
+  }
+  for (const AggSpec& a : Q.aggs) {
+    for (const std::string* col : {&a.column, &a.column2}) {
+      if (col->empty()) continue;
+      const bool mv = mv_of(*col) != 0;
+      if (rc) return rc;
+      if (is_mv_agg(a.type)) {
+        if (type_of(*col) == T_STRING)
+          return fail(PINOT_AMD_EINVAL, "multi-value aggregation %d over STRING column %s", a.type, col->c_str());
+        if (!mv && type_of(*col) >= 0)
+          return fail(PINOT_AMD_EUNSUPPORTED, "multi-value aggregation %d over single-value column %s", a.type, col->c_str());
+      } else if (mv) {
+        return fail(PINOT_AMD_EUNSUPPORTED, "single-value aggregation %d over multi-value column %s (use its MV function)",
+                    a.type, col->c_str());
+      }
+    }
+  }
+  return rc;
+}
+
+// The single-value twins of a multi-value column's per-doc count / sum / min / max, which the *MV aggregations
+// aggregate: built on the device (mv_reduce_kernel), staged as raw columns beside the source at the first query
+// that needs each ("<col>$mvcount" INT; "$mvsum" LONG, the exact sum; "$mvsumd" DOUBLE, summed in value order;
+// "$mvmin" / "$mvmax" of the column's type, DOUBLE for FLOAT / DOUBLE and then never NaN).
+static const char* mv_twin_suffix(int op) {
+  switch (op) {
+    case MV_RED_COUNT: return "$mvcount";
+    case MV_RED_SUM_I64: return "$mvsum";
+    case MV_RED_SUM_F64: return "$mvsumd";
+    case MV_RED_MIN: return "$mvmin";
+    default: return "$mvmax";
+  }
+}
+// whether every per-doc sum of the column fits int64: maxNumberOfMultiValues x the dictionary's largest magnitude
+static bool mv_sum_exact(const Column& c) {
+  if (is_float(c.type)) return false;
+  if (c.dict_i.empty()) return true;
+  auto mag = [](int64_t v) { return v < 0 ? -(__int128)v : (__int128)v; };
+  const __int128 m = std::max(mag(c.dict_i.front()), mag(c.dict_i.back()));
+  return (__int128)std::max(c.mv_max, 1) * m < ((__int128)1 << 63);
+}
+static int derive_mv_twin(pinot_amd_segment* s, const std::string& col, int op, std::string* out_name) {
+  *out_name = col + mv_twin_suffix(op);
+  if (s->cols.count(*out_name)) return 0;
+  const Column& c = *s->cols.at(col);
+  const int64_t nd = s->num_docs;
+  const bool fl = is_float(c.type);
+  const int ttype = op == MV_RED_COUNT ? T_INT : op == MV_RED_SUM_I64 ? T_LONG : (op == MV_RED_SUM_F64 || fl) ? T_DOUBLE : c.type;
+  const int vs = value_size(ttype);
+  std::vector<uint64_t> h((size_t)nd);
+  if (nd > 0) {
+    DevBuf out;
+    if (int rc = out.alloc((size_t)nd * 8)) return rc;
+    HIP_OK(launch_mv_reduce(mv_dev(c, nd), c.dict.p, c.type, op, (unsigned long long*)out.p, nullptr));
+    HIP_OK(hipMemcpy(h.data(), out.p, (size_t)nd * 8, hipMemcpyDeviceToHost));
+  }
+  // the kernel's words -> the bytes of a PASS_THROUGH raw forward index (header of 7 big-endian ints, no chunk
+  // offsets read), staged like any raw column: it gets its value range and a packed twin where that pays
+  constexpr size_t kHdr = 28;
+  std::vector<uint8_t> file(kHdr + (size_t)nd * vs, 0);
+  const uint32_t hdr[7] = {4u, 0u, 0u, (uint32_t)vs, (uint32_t)nd, 0u, (uint32_t)kHdr};
+  for (int i = 0; i < 7; ++i)
+    for (int b = 0; b < 4; ++b) file[4 * i + b] = (uint8_t)(hdr[i] >> (24 - 8 * b));
+  for (int64_t d = 0; d < nd; ++d) {
+    uint64_t u = h[(size_t)d];
+    if (op == MV_RED_MIN || op == MV_RED_MAX) {
+      if (fl) {  // Double.compare's key back to the double's bits; nothing entered: +inf / -inf
+        double x = op == MV_RED_MIN ? INFINITY : -INFINITY;
+        if (!(op == MV_RED_MIN ? u == ~0ull : u == 0ull)) {
+          const uint64_t b = (u >> 63) ? (u & 0x7FFFFFFFFFFFFFFFull) : ~u;
+          memcpy(&x, &b, 8);
+        }
+        memcpy(&u, &x, 8);
+      } else {
+        u ^= 1ull << 63;
+      }
+    }
+    uint8_t* o = &file[kHdr + (size_t)d * vs];
+    for (int b = 0; b < vs; ++b) o[b] = (uint8_t)(u >> (8 * (vs - 1 - b)));
+  }
+  pinot_amd_column_spec spec{};
+  spec.name = out_name->c_str();
+  spec.stored_type = ttype;
+  spec.encoding = ENC_RAW;
+  spec.h_fwd = file.data();
+  spec.fwd_size = file.size();
+  return pinot_amd_segment_add_column(s, &spec);
 }
 
 static int build_merged_keys_uncached(const std::vector<pinot_amd_segment*>& segs, const std::string& col,
@@ -2891,6 +3294,15 @@ static int read_counters(pinot_amd_result* r, std::vector<unsigned long long>* c
 // then the candidate records sorted by (segment, key, docId), each segment's first offset + limit rows cut, their
 // columns gathered by docId, and the combine on the host over those rows: by value (INT / LONG numerically, FLOAT /
 // DOUBLE as Double.compare, STRING as String.compareTo, DESC reversed), ties by ascending (segment, docId).
+// multi-value leaves: the docs holding any value of each leaf's dictId set, into its zeroed docId bitset
+static int run_mv_leaves(pinot_amd_result* r, hipStream_t st) {
+  for (const auto& ml : r->mv_leaves) {
+    HIP_OK(hipMemsetAsync(ml.bitset->p, 0, ml.bitset->n, st));
+    HIP_OK(launch_mv_match(mv_dev(*ml.col, ml.num_docs), ml.set, (uint32_t*)ml.bitset->p, st));
+  }
+  return 0;
+}
+
 static int run_selection(pinot_amd_result* r) {
   hipStream_t st = r->stream;
   r->compacted = false;
@@ -2909,6 +3321,7 @@ static int run_selection(pinot_amd_result* r) {
     HIP_OK(hipEventRecord(r->ev1, st));
     return 0;
   }
+  if (int rc = run_mv_leaves(r, st)) return rc;
   if (!r->inv_leaves.empty())
     HIP_OK(launch_expand_jobs(r->d_expand_jobs.p, (int32_t)r->inv_leaves.size(), r->expand_total, st));
   HIP_OK(hipMemsetAsync(r->tk_ctr.p, 0, 16, st));
@@ -3058,6 +3471,7 @@ static int run_plan(pinot_amd_result* r) {
     }
   }
   HIP_OK(hipEventRecord(r->ev0, st));
+  if (int rc = run_mv_leaves(r, st)) return rc;
   // inverted-index leaves: expand roaring containers into dense doc bitsets
   bool all_fused = !r->launches.empty();
   for (auto& L : r->launches) all_fused &= L.fused;
@@ -3365,6 +3779,7 @@ struct PlanBuild {
   pinot_amd_query filter_q;  // FilterPlanNode only: no projection, no aggregation
   pinot_amd_query raw_gb_q;  // group-by columns redirected to the derived dictionary of raw columns
   pinot_amd_query sel_q;     // a selection with LIMIT 0: without its ORDER BY (EmptySelectionOperator)
+  pinot_amd_query mv_q;      // the *MV aggregations redirected to the twins of their columns' per-doc reductions
   const pinot_amd_query* Qp = nullptr;
   // slots and leaves (leaves)
   std::vector<std::string> slot_cols;
@@ -3444,6 +3859,7 @@ struct PlanBuild {
 // the query the plan is built for: the filter alone (FilterPlanNode), or the query with raw GROUP BY columns
 // redirected to their derived dictionaries and the twins of its transformed keys built where they are missing
 int PlanBuild::raw_keys() {
+  if (int rc = check_mv_query(*qq, segs.data(), n, filter_only)) return rc;
   if (filter_only) filter_q.preds = qq->preds;  // FilterPlanNode only: no projection, no aggregation
   Qp = filter_only ? &filter_q : qq;
   if (sel && qq->sel_limit + qq->sel_offset == 0 && !qq->sel_order.empty()) {
@@ -3481,6 +3897,36 @@ int PlanBuild::raw_keys() {
     if (Qp != &raw_gb_q) { raw_gb_q = *Qp; Qp = &raw_gb_q; }
     for (auto* s : segs)
       if (int rc = derive_raw_group_dictionary(s, g, &raw_gb_q.group_by[j])) return rc;
+  }
+  // the *MV aggregations read the twins of their column's per-doc count / sum / min / max (check_mv_query has
+  // refused what cannot run: from here only the twins' own staging can fail). AVGMV: the sum's twin, then the
+  // count's; MINMAXRANGEMV: the min's, then the max's. The per-doc sum is the exact LONG twin when it fits int64
+  // in every segment of the batch, else the DOUBLE one (one type per slot across a launch's segments).
+  if (std::any_of(Qp->aggs.begin(), Qp->aggs.end(), [](const AggSpec& a) { return is_mv_agg(a.type); })) {
+    mv_q = *Qp;
+    Qp = &mv_q;
+    for (AggSpec& a : mv_q.aggs) {
+      if (!is_mv_agg(a.type)) continue;
+      const std::string col = a.column;
+      for (auto* s : segs)
+        if (!s->cols.count(col)) return fail(PINOT_AMD_EINVAL, "segment %s has no column %s", s->name.c_str(), col.c_str());
+      bool exact = true;
+      for (auto* s : segs) exact &= mv_sum_exact(*s->cols.at(col));
+      int op1 = -1, op2 = -1;
+      switch (a.type) {
+        case PINOT_AMD_AGG_COUNTMV: op1 = MV_RED_COUNT; break;
+        case PINOT_AMD_AGG_SUMMV: op1 = exact ? MV_RED_SUM_I64 : MV_RED_SUM_F64; break;
+        case PINOT_AMD_AGG_MINMV: op1 = MV_RED_MIN; break;
+        case PINOT_AMD_AGG_MAXMV: op1 = MV_RED_MAX; break;
+        case PINOT_AMD_AGG_AVGMV: op1 = exact ? MV_RED_SUM_I64 : MV_RED_SUM_F64; op2 = MV_RED_COUNT; break;
+        default: op1 = MV_RED_MIN; op2 = MV_RED_MAX; break;
+      }
+      for (auto* s : segs) {
+        if (int rc = derive_mv_twin(s, col, op1, &a.column)) return rc;
+        if (op2 >= 0)
+          if (int rc = derive_mv_twin(s, col, op2, &a.column2)) return rc;
+      }
+    }
   }
   return 0;
 }
@@ -3852,6 +4298,30 @@ int PlanBuild::accs() {
     const AccReq lane_count{-1, ACC_SUM_I64, EXPR_ONE, -1, 0, lane};
     if (a.type == PINOT_AMD_AGG_COUNT) {
       if (lane) agg_req[ai] = find_req(lane_count);
+      continue;
+    }
+    if (is_mv_agg(a.type)) {
+      // over the twins raw_keys redirected the aggregation to: COUNTMV sums the per-doc counts, SUMMV / AVGMV the
+      // per-doc sums (exactly in 128 bits for the LONG twin), MINMV / MAXMV / MINMAXRANGEMV fold the per-doc
+      // minima / maxima (no twin holds NaN: value < min / value > max never let one in); AVGMV divides by the
+      // sum of the counts, its second accumulator
+      const Column& t = *segs[0]->cols.at(a.column);
+      const int sl = slot_of(a.column);
+      const int sum_op = is_float(t.type) ? ACC_SUM_F64 : ACC_SUM_I128;
+      switch (a.type) {
+        case PINOT_AMD_AGG_COUNTMV: agg_req[ai] = find_req({sl, ACC_SUM_I64, PINOT_AMD_EXPR_COLUMN, -1, 0, lane}); break;
+        case PINOT_AMD_AGG_SUMMV: agg_req[ai] = find_req({sl, sum_op, PINOT_AMD_EXPR_COLUMN, -1, 0, lane}); break;
+        case PINOT_AMD_AGG_MINMV: agg_req[ai] = find_req({sl, ACC_MIN, PINOT_AMD_EXPR_COLUMN, -1, 0, lane}); break;
+        case PINOT_AMD_AGG_MAXMV: agg_req[ai] = find_req({sl, ACC_MAX, PINOT_AMD_EXPR_COLUMN, -1, 0, lane}); break;
+        case PINOT_AMD_AGG_AVGMV:
+          agg_req[ai] = find_req({sl, sum_op, PINOT_AMD_EXPR_COLUMN, -1, 0, lane});
+          agg_req2[ai] = find_req({slot_of(a.column2), ACC_SUM_I64, PINOT_AMD_EXPR_COLUMN, -1, 0, lane});
+          break;
+        default:
+          agg_req[ai] = find_req({sl, ACC_MIN, PINOT_AMD_EXPR_COLUMN, -1, 1, lane});
+          agg_req2[ai] = find_req({slot_of(a.column2), ACC_MAX, PINOT_AMD_EXPR_COLUMN, -1, 1, lane});
+          break;
+      }
       continue;
     }
     const Column& c = *segs[0]->cols.at(a.column);
@@ -5568,6 +6038,9 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
   b.sel = sel;
   b.r = r;
   if (int rc = b.raw_keys()) return rc;
+  // (twins staged for the *MV aggregations bumped their segments' generations: the plan is kept under the identity
+  // the re-issued query will compute)
+  if (b.Qp == &b.mv_q) r->plan_key = plan_identity(*qq, b.segs, filter_only);
   clk.mark("raw_keys");
   if (int rc = b.lanes()) return rc;
   if (int rc = b.leaves()) return rc;
@@ -5645,6 +6118,8 @@ static int execute_distinct(pinot_amd_query* qq, pinot_amd_segment* const* segs_
                             pinot_amd_result** out) {
   if (!segs_in || n < 1 || !out) return fail(PINOT_AMD_EINVAL, "execute: bad arguments");
   const pinot_amd_query& U = *qq;
+  // (before the value-set queries are derived: theirs would GROUP BY the aggregation's multi-value column)
+  if (int rc = check_mv_query(U, segs_in, n, false)) return rc;
   const pinot_amd_query dflt;
   if (!U.group_by.empty() && U.limit >= 0 && !U.order_by.empty()) {
     std::vector<bool> seen(U.group_by.size(), false);
@@ -6040,6 +6515,7 @@ int pinot_amd_result_algorithmic_bytes(pinot_amd_result* r, double* h_bytes) {
   bool all_fused = !r->launches.empty();
   for (const auto& L : r->launches) all_fused &= L.fused;
   for (const auto& il : r->inv_leaves) b += il.alg_bytes + (all_fused ? 0.0 : il.bitset_bytes);
+  for (const auto& ml : r->mv_leaves) b += ml.alg_bytes + ml.bitset_bytes;
   if (r->topk)  // the gathered columns of the rows fetched (the filter and ORDER BY columns: the launches below)
     b += (double)r->sel_nrows * r->sel_key_bytes;
   for (size_t li = 0; li < r->launches.size(); ++li) {
@@ -6407,10 +6883,20 @@ static void final_value(const pinot_amd_result* r, const uint64_t* A, int a, dou
       v = n ? s / (double)n : -INFINITY;  // AvgAggregationFunction: empty -> DEFAULT_FINAL_RESULT
       break;
     }
+    case PINOT_AMD_AGG_AVGMV: {  // AvgPair(sum of values, count of values)
+      int64_t ex;
+      const double s = op == ACC_SUM_F64 ? ([&] { double d; memcpy(&d, &w, 8); return d; })() : sum128(&ex);
+      const uint64_t n = A[r->agg_acc2[a]];
+      v = n ? s / (double)n : -INFINITY;
+      break;
+    }
     case PINOT_AMD_AGG_MIN:
     case PINOT_AMD_AGG_MAX:
+    case PINOT_AMD_AGG_MINMV:
+    case PINOT_AMD_AGG_MAXMV:
       v = decode_ordered(w, op);
       break;
+    case PINOT_AMD_AGG_MINMAXRANGEMV:
     case PINOT_AMD_AGG_MINMAXRANGE:  // MinMaxRangeAggregationFunction.extractFinalResult: max - min
       v = decode_ordered(A[r->agg_acc2[a]], ACC_MAX) - decode_ordered(w, ACC_MIN);
       break;
@@ -6607,6 +7093,12 @@ int pinot_amd_result_fetch_intermediate(pinot_amd_result* r, int64_t cap, double
           out[1] = cnt;
           break;
         }
+        case PINOT_AMD_AGG_AVGMV:  // AvgPair(sum of values, count of values)
+          if (r->q.acc_op[acc] == ACC_SUM_F64) memcpy(&out[0], &A[acc], 8);
+          else out[0] = (double)(__int128)(((unsigned __int128)A[acc + 1] << 64) | (unsigned __int128)A[acc]);
+          out[1] = (double)A[r->agg_acc2[a]];
+          break;
+        case PINOT_AMD_AGG_MINMAXRANGEMV:
         case PINOT_AMD_AGG_MINMAXRANGE:  // MinMaxRangePair(min, max)
           out[0] = decode_ordered(A[acc], ACC_MIN);
           out[1] = decode_ordered(A[r->agg_acc2[a]], ACC_MAX);

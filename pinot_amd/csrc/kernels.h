@@ -116,6 +116,41 @@ hipError_t derive_dictionary(const uint8_t* d_src, int type, int src, const DevK
 hipError_t launch_remap_dict_ids(int32_t* ids, int64_t n, const int32_t* map, int64_t card, hipStream_t st);
 hipError_t launch_sorted_dict_ids(const int32_t* starts, int64_t card, int64_t n, const int32_t* map, int32_t* ids,
                                   hipStream_t st);
+// Multi-value columns. A staged dictionary-encoded MV forward index (FixedBitMVForwardIndexWriter's file, all
+// big-endian): `words` is the 4-byte aligned file; the start-bit bitmap begins at dword bm_word0 (MSB-first, bit i
+// set = value i starts a doc), the fixed-bit dictId stream at bit raw_bit0 of the file. tile_first_doc[t] = start bits
+// before value t * kMvTileValues: the only derived index.
+constexpr int kMvTileValues = 4096;
+struct DevMvColumn {
+  const uint32_t* words;
+  int64_t bm_word0, raw_bit0;
+  int64_t num_values, num_docs;
+  const int32_t* tile_first_doc;
+  int32_t bits, pad;
+};
+// An ANY-match predicate's resolved dictId set
+enum : int32_t { MV_SET_RANGE = 0 /* lo <= dictId < hi */, MV_SET_ACCEPT = 1 /* bit dictId of accept, card <= 64 */,
+                 MV_SET_LDS = 2 /* bit dictId of set, staged in LDS */, MV_SET_HBM = 3 /* ... read in place */ };
+struct DevMvSet {
+  int32_t mode, set_words;
+  int64_t lo, hi, card;
+  uint64_t accept;
+  const uint32_t* set;
+};
+enum : int32_t { MV_RED_COUNT = 0, MV_RED_SUM_I64 = 1, MV_RED_SUM_F64 = 2, MV_RED_MIN = 3, MV_RED_MAX = 4 };
+int64_t mv_num_tiles(int64_t num_values);
+// tile_first_doc: mv_num_tiles(num_values) entries (at least one allocated); total[0] = the bitmap's popcount
+hipError_t launch_mv_index(const DevMvColumn& c, int32_t* tile_first_doc, long long* total, hipStream_t st);
+// flags |= 1: bit 0 unset, 4: a chunk offset header entry disagrees with the bitmap's rank, 8: a doc longer than
+// max_values
+hipError_t launch_mv_validate(const DevMvColumn& c, int32_t docs_per_chunk, int32_t num_chunks, int32_t max_values,
+                              uint32_t* flags, hipStream_t st);
+hipError_t launch_mv_read(const DevMvColumn& c, int32_t* offsets, int32_t* ids, hipStream_t st);
+// ORs the docs with a matching value into `bitset` (32-bit words of the dense docId bitset, zeroed by the caller)
+hipError_t launch_mv_match(const DevMvColumn& c, const DevMvSet& s, uint32_t* bitset, hipStream_t st);
+// one word per doc (mv_reduce_kernel); dict: the column's little-endian dictionary of `type`
+hipError_t launch_mv_reduce(const DevMvColumn& c, const void* dict, int type, int op, unsigned long long* out,
+                            hipStream_t st);
 size_t sort_rows_scratch(int64_t n);
 hipError_t sort_rows_by_key(const uint64_t* keys, int nwk, const int* word_bits, const uint64_t* acc, int nacc, int64_t n,
                             void* scratch, uint64_t* keys_out, uint64_t* acc_out, hipStream_t st);

@@ -379,8 +379,12 @@ __device__ double segsel_final(const SegSelStage& g, const DevQuery& q, const ui
   switch (g.agg_type) {
     case PINOT_AMD_AGG_COUNT: return (double)cnt;
     case PINOT_AMD_AGG_AVG: return cnt ? sum() / (double)cnt : -__builtin_inf();
+    case PINOT_AMD_AGG_AVGMV: return A(g.acc2) ? sum() / (double)A(g.acc2) : -__builtin_inf();  // AvgPair(sum, value count)
     case PINOT_AMD_AGG_MIN:
-    case PINOT_AMD_AGG_MAX: return decode_ordered_dev(w, op);
+    case PINOT_AMD_AGG_MAX:
+    case PINOT_AMD_AGG_MINMV:
+    case PINOT_AMD_AGG_MAXMV: return decode_ordered_dev(w, op);
+    case PINOT_AMD_AGG_MINMAXRANGEMV:
     case PINOT_AMD_AGG_MINMAXRANGE: return decode_ordered_dev(A(g.acc2), ACC_MAX) - decode_ordered_dev(w, ACC_MIN);
     default: return sum();
   }

@@ -199,6 +199,7 @@ def merge_result(result, scratch=None, group=None, stream=None, gather_max_bytes
     import torch
     import torch.distributed as dist
     _refuse_filtered_aggregations(getattr(result, "qc", None))
+    _refuse_multi_value(getattr(result, "qc", None), result)
     cur = torch.cuda.current_stream() if torch.cuda.is_available() else None
     if stream is not None and cur is not None:
         handle = int(getattr(stream, "cuda_stream", stream))
@@ -366,6 +367,7 @@ def merge_groups(qc, groups: dict, group=None) -> dict:
     import torch.distributed as dist
     from .query import merge_partial
     _refuse_filtered_aggregations(qc)
+    _refuse_multi_value(qc)
     world = dist.get_world_size(group)
     parts = [None] * world
     dist.all_gather_object(parts, groups, group=group)
@@ -403,6 +405,17 @@ def _refuse_filtered_aggregations(qc) -> None:
     """Filtered aggregations (FILTER (WHERE ...)) run on one GPU: no cross-rank merge of them is tested."""
     if qc is not None and any(getattr(a, "filter", None) is not None for a in qc.aggregations):
         raise ValueError("filtered aggregations (FILTER (WHERE ...)) are not covered by the cross-rank merge")
+
+
+def _refuse_multi_value(qc, result=None) -> None:
+    """Multi-value columns run on one GPU: a query with an *MV aggregation or a predicate on an MV column has no
+    tested cross-rank merge."""
+    from .query import MV_FUNCS
+    if qc is not None and any(a.func in MV_FUNCS for a in qc.aggregations):
+        raise ValueError("multi-value aggregations (COUNTMV / SUMMV / ...) are not covered by the cross-rank merge")
+    cols = getattr(result, "mv_columns", None)
+    if cols:
+        raise ValueError(f"a filter on the multi-value column(s) {', '.join(cols)} is not covered by the cross-rank merge")
 
 
 def _refuse_key_transforms(group_by: Sequence[str]) -> None:

@@ -27,16 +27,17 @@ import numpy as np
 
 from . import _lib
 from ._lib import ColumnSpec, KeyTransformSpec, PredicateSpec, check, lib
-from .query import (KEY_TRANSFORMS, TIME_UNITS, TRUNC_UNITS, VALUE_SET_FUNCS, DistinctSize, FinalValue, JavaDouble,
+from .query import (KEY_TRANSFORMS, MV_FUNCS, TIME_UNITS, TRUNC_UNITS, VALUE_SET_FUNCS, DistinctSize, FinalValue, JavaDouble,
                     QueryContext, filter_text, fold_distinct_count, hists_from_csr, key_transform, parse_sql, reduce_rows,
                     server_table, sets_from_csr, split_distinct_count, to_cnf)
 from .segment import ColumnBuffers, SegmentBuffers, DOUBLE, FLOAT, INT, LONG, STRING
 
 TYPE_CODE = {INT: 0, LONG: 1, FLOAT: 2, DOUBLE: 3, STRING: 4}
-ENC_CODE = {"FIXED_BIT": 0, "RAW": 1, "SORTED": 2}
+ENC_CODE = {"FIXED_BIT": 0, "RAW": 1, "SORTED": 2, "FIXED_BIT_MV": 3}
 PRED_CODE = {"EQ": 0, "NOT_EQ": 1, "IN": 2, "NOT_IN": 3, "RANGE": 4}
 AGG_CODE = {"COUNT": 0, "SUM": 1, "MIN": 2, "MAX": 3, "SUMLONG": 4, "AVG": 5, "MINMAXRANGE": 6,
-            "DISTINCTCOUNT": 7, "PERCENTILE": 8, "DISTINCTSUM": 9, "DISTINCTAVG": 10}
+            "DISTINCTCOUNT": 7, "PERCENTILE": 8, "DISTINCTSUM": 9, "DISTINCTAVG": 10,
+            "COUNTMV": 11, "SUMMV": 12, "MINMV": 13, "MAXMV": 14, "AVGMV": 15, "MINMAXRANGEMV": 16}
 EXPR_CODE = {"MUL": 1, "SUB": 2, "ADD": 3}
 
 
@@ -87,9 +88,21 @@ class ImmutableSegment:
         if cb.inverted:
             spec.h_inverted = C.cast(C.c_char_p(cb.inverted), C.c_void_p)
             spec.inverted_size = len(cb.inverted)
-        check(lib().pinot_amd_segment_add_column(self._h, C.byref(spec)), f"add_column({cb.name})")
+        if cb.multi_value:  # the whole FixedBitMVForwardIndexWriter file, validated on the device
+            check(lib().pinot_amd_segment_add_mv_column(self._h, C.byref(spec), cb.total_values, cb.max_values),
+                  f"add_mv_column({cb.name})")
+        else:
+            check(lib().pinot_amd_segment_add_column(self._h, C.byref(spec)), f"add_column({cb.name})")
         del keep
         self.columns[cb.name] = cb
+
+    def mv_info(self, column: str):
+        """(totalNumberOfEntries, maxNumberOfMultiValues) of a multi-value column, None for a single-value one."""
+        total, mx = C.c_int64(), C.c_int32()
+        rc = lib().pinot_amd_segment_column_mv_info(self._h, column.encode(), C.byref(total), C.byref(mx))
+        if rc < 0:
+            raise KeyError(column)
+        return (total.value, mx.value) if rc else None
 
     @property
     def handle(self):
@@ -261,7 +274,8 @@ class QueryResult:
         self.qc = qc
         # per qc aggregation: ('direct', native_idx) | ('avg', sum_idx, count_idx) | ('range', native_idx) |
         # ('distinct', native_idx, stored type of the column): DISTINCTCOUNT executed by the library |
-        # ('hist', ...) PERCENTILE | ('dset', ...) DISTINCTSUM / DISTINCTAVG, likewise
+        # ('hist', ...) PERCENTILE | ('dset', ...) DISTINCTSUM / DISTINCTAVG, likewise |
+        # ('avgmv', native_idx): AVGMV's AvgPair (sum of values, count of values) from fetch_intermediate
         self._agg_slots = agg_slots
         self._key_types = key_types
         self._merged_reached = None      # numGroupsLimitReached OR-ed over ranks by dist.merge_result
@@ -391,7 +405,7 @@ class QueryResult:
                                        vals.ctypes.data_as(C.POINTER(C.c_double)),
                                        vals_i.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(got)), "fetch")
         pairs = None
-        if any(s[0] == "range" for s in self._agg_slots):
+        if any(s[0] in ("range", "avgmv") for s in self._agg_slots):
             pairs = np.zeros(n * nnat * 2, dtype=np.float64)
             got2 = C.c_int64()
             check(L.pinot_amd_result_fetch_intermediate(self._h, n, pairs.ctypes.data_as(C.POINTER(C.c_double)),
@@ -482,7 +496,10 @@ class QueryResult:
             elif slot[0] == "range":
                 pr = pairs[:n * nnat * 2].reshape(n, nnat, 2)
                 acols.append(list(zip(pr[:, slot[1], 0].tolist(), pr[:, slot[1], 1].tolist())))
-            elif a.func in ("COUNT", "SUMLONG"):
+            elif slot[0] == "avgmv":
+                pr = pairs[:n * nnat * 2].reshape(n, nnat, 2)
+                acols.append(list(zip(pr[:, slot[1], 0].tolist(), pr[:, slot[1], 1].astype(np.int64).tolist())))
+            elif a.func in ("COUNT", "SUMLONG", "COUNTMV"):
                 acols.append(vi[:, slot[1]].tolist())
             else:
                 acols.append(v[:, slot[1]].tolist())
@@ -807,7 +824,10 @@ class ServerQueryExecutor:
                 if key in native:
                     return native.index(key)
                 idx = C.c_int32()
-                if AGG_CODE[func] > AGG_CODE["DISTINCTCOUNT"]:  # the functions with a literal argument's entry point
+                if func in MV_FUNCS:  # the multi-value functions' entry point
+                    check(L.pinot_amd_query_add_aggregation_mv(qh, AGG_CODE[func], column.encode(), C.byref(idx)),
+                          f"add_aggregation_mv({func})")
+                elif AGG_CODE[func] > AGG_CODE["DISTINCTCOUNT"]:  # the functions with a literal argument's entry point
                     check(L.pinot_amd_query_add_aggregation_param(qh, AGG_CODE[func], column.encode(),
                                                                   0.0 if param is None else param, C.byref(idx)),
                           f"add_aggregation_param({func})")
@@ -847,6 +867,11 @@ class ServerQueryExecutor:
                                       add(a.func, a.column, None, a.param, a.filter), col.stored_type))  # (a FILTER: refused there)
                 elif a.func == "MINMAXRANGE":  # MinMaxRangePair (min, max), NaN-skipping, in the library
                     agg_slots.append(("range", add("MINMAXRANGE", a.column, a.expr, None, a.filter)))
+                elif a.func in MV_FUNCS:  # over the column's per-doc twins, in the library
+                    if a.expr is not None or a.column == "*":
+                        raise ValueError(f"{a.func} takes one multi-value column")
+                    kind = {"AVGMV": "avgmv", "MINMAXRANGEMV": "range"}.get(a.func, "direct")
+                    agg_slots.append((kind, add(a.func, a.column, None, None, a.filter)))
                 else:
                     agg_slots.append(("direct", add(a.func, a.column, a.expr, None, a.filter)))
             if not qc.aggregations and qc.group_by:
@@ -865,4 +890,7 @@ class ServerQueryExecutor:
         key_types = [LONG if key_transform(g) is not None else first.columns[g].stored_type for g in qc.group_by]
         res = QueryResult(rh, qc, agg_slots, key_types)
         res._native_aggs = native
+        # the multi-value columns the query filters on (dist.merge_result refuses such a result)
+        res.mv_columns = sorted({p.column for clause in qc.cnf for p, _ in clause
+                                 if getattr(first.columns.get(p.column), "multi_value", False)})
         return res

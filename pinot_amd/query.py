@@ -20,7 +20,11 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 AGG_FUNCS = ("COUNT", "SUM", "MIN", "MAX", "AVG", "SUMLONG", "MINMAXRANGE", "DISTINCTCOUNT", "PERCENTILE",
-             "DISTINCTSUM", "DISTINCTAVG")
+             "DISTINCTSUM", "DISTINCTAVG", "COUNTMV", "SUMMV", "MINMV", "MAXMV", "AVGMV", "MINMAXRANGEMV")
+# the aggregations over a multi-value column: every value of a matching doc counts (CountMV / SumMV / MinMV / MaxMV /
+# AvgMV / MinMaxRangeMVAggregationFunction); partials as their SV parents': AVGMV (sum, count of values),
+# MINMAXRANGEMV (min, max)
+MV_FUNCS = ("COUNTMV", "SUMMV", "MINMV", "MAXMV", "AVGMV", "MINMAXRANGEMV")
 # the aggregations answered from a (group-by columns..., column) COUNT(*) query: each group's histogram over the
 # column's distinct values (split_distinct_count)
 VALUE_SET_FUNCS = ("DISTINCTCOUNT", "PERCENTILE", "DISTINCTSUM", "DISTINCTAVG")
@@ -164,6 +168,8 @@ def agg_head(word: str):
     w = word.upper()
     if w in AGG_FUNCS:
         return w, None
+    if w.replace("_", "") in MV_FUNCS:  # Pinot canonicalises function names: SUM_MV is SUMMV
+        return w.replace("_", ""), None
     m = _PERCENTILE_N.match(w)
     if m:
         return "PERCENTILE", check_percentile(m.group(1))
@@ -180,6 +186,7 @@ class Aggregation:
     (MultiplicationTransformFunction / SubtractionTransformFunction / AdditionTransformFunction;
     CAST(x AS DOUBLE) operands are accepted: every transform already computes in double)."""
     func: str          # COUNT SUM MIN MAX AVG SUMLONG MINMAXRANGE DISTINCTCOUNT PERCENTILE DISTINCTSUM DISTINCTAVG
+                       # COUNTMV SUMMV MINMV MAXMV AVGMV MINMAXRANGEMV
     column: str
     alias: Optional[str] = None
     expr: Optional[Tuple[str, str, str]] = None
@@ -819,10 +826,10 @@ def final_value(func: str, partial, param=None):
     (MinMaxRangeAggregationFunction: MinMaxRangePair(+inf, -inf) when no doc matched), DISTINCTCOUNT -> the set's
     size, PERCENTILE (param: the percentile) -> percentile_select over the histogram, DISTINCTSUM / DISTINCTAVG ->
     the set's sum (/ its size), others unchanged."""
-    if func == "AVG":
+    if func in ("AVG", "AVGMV"):
         s, c = partial
         return s / c if c else float("-inf")
-    if func == "MINMAXRANGE":
+    if func in ("MINMAXRANGE", "MINMAXRANGEMV"):
         mn, mx = partial
         return mx - mn
     if func == "DISTINCTCOUNT":
@@ -844,15 +851,15 @@ _HISTOGRAM_FINALS = frozenset(("PERCENTILE", "DISTINCTSUM", "DISTINCTAVG"))
 
 def merge_partial(func: str, a, b):
     """AggregationFunction.merge (used by the combine and broker reduce)."""
-    if func in ("COUNT", "SUM", "SUMLONG"):
+    if func in ("COUNT", "SUM", "SUMLONG", "COUNTMV", "SUMMV"):
         return a + b
-    if func == "MIN":
+    if func in ("MIN", "MINMV"):
         return min(a, b)
-    if func == "MAX":
+    if func in ("MAX", "MAXMV"):
         return max(a, b)
-    if func == "AVG":
+    if func in ("AVG", "AVGMV"):
         return (a[0] + b[0], a[1] + b[1])
-    if func == "MINMAXRANGE":
+    if func in ("MINMAXRANGE", "MINMAXRANGEMV"):
         return (min(a[0], b[0]), max(a[1], b[1]))
     if func in ("DISTINCTCOUNT", "DISTINCTSUM", "DISTINCTAVG"):
         return a | b

@@ -15,6 +15,8 @@ CPU oracle see the same buffers the reference's readers see:
   plus chunk offsets (.../io/writer/impl/BaseChunkForwardIndexWriter.java:131-165,
   read by ``FixedBytePower2ChunkSVForwardIndexReader`` / ``BaseChunkForwardIndexReader``
   .../readers/forward/BaseChunkForwardIndexReader.java:60-105);
+* dictionary-encoded multi-value forward index: chunk offsets, start-bit bitmap, fixed-bit dictIds
+  (``FixedBitMVForwardIndexWriter`` / ``FixedBitMVForwardIndexReader``);
 * sorted dictionaries of big-endian fixed-width values, strings padded with NUL
   (``IntDictionary``/``LongDictionary``/``FloatDictionary``/``DoubleDictionary``/``StringDictionary``);
 * bitmap inverted index: (cardinality+1) big-endian absolute offsets followed by
@@ -97,6 +99,78 @@ def unpack_fixed_bit(buf: bytes, bits: int, n: int) -> np.ndarray:
     allbits = np.unpackbits(a)[: n * bits].reshape(n, bits).astype(np.int64)
     w = (1 << np.arange(bits - 1, -1, -1, dtype=np.int64))
     return (allbits * w).sum(axis=1).astype(np.int32)
+
+
+# --------------------------------------------------------------------------- multi-value fwd
+MV_PREFERRED_VALUES_PER_CHUNK = 2048  # FixedBitMVForwardIndexWriter.PREFERRED_NUM_VALUES_PER_CHUNK
+
+
+def mv_docs_per_chunk(num_docs: int, total_values: int) -> int:
+    """FixedBitMVForwardIndexWriter.java:79-80: ceil(2048 / (float) (totalNumValues / numDocs)), the inner division
+    Java's int division (5 docs of 9 values average 1, not 1.8)."""
+    avg = np.float32(total_values // num_docs)
+    return int(np.ceil(np.float32(MV_PREFERRED_VALUES_PER_CHUNK) / avg))
+
+
+def mv_fwd_bytes(doc_id_lists, bits: int) -> bytes:
+    """Dictionary-encoded multi-value forward index as FixedBitMVForwardIndexWriter writes it
+    (.../io/writer/impl/FixedBitMVForwardIndexWriter.java:36-101,143-158), all big-endian: numChunks int32 chunk
+    offsets (entry k = the value index where doc k * docsPerChunk starts), a bitmap of ceil(totalNumValues / 8) bytes,
+    MSB-first (PinotDataBitSet: bit i set = value i starts a doc), and the values' dictIds in the fixed-bit stream
+    of the SV forward index. Every doc has at least one value; a doc's values keep their order and duplicates.
+    No docs: an empty buffer."""
+    lens = np.fromiter((len(d) for d in doc_id_lists), dtype=np.int64, count=len(doc_id_lists))
+    if lens.size == 0:
+        return b""
+    return mv_fwd_bytes_flat(np.concatenate([np.asarray(d, dtype=np.int64) for d in doc_id_lists]), lens, bits)
+
+
+def mv_fwd_bytes_flat(dict_ids: np.ndarray, lens: np.ndarray, bits: int) -> bytes:
+    """:func:`mv_fwd_bytes` of docs given as their concatenated dictIds and the docs' lengths (large columns)."""
+    lens = np.asarray(lens, dtype=np.int64)
+    nd = int(lens.size)
+    if nd == 0:
+        return b""
+    if int(lens.min()) < 1:
+        raise ValueError("a multi-value doc needs at least one value")
+    starts = np.r_[0, np.cumsum(lens)[:-1]]
+    total = int(lens.sum())
+    if total != len(dict_ids):
+        raise ValueError("the docs' lengths do not add up to the values")
+    dpc = mv_docs_per_chunk(nd, total)
+    header = starts[::dpc].astype(">i4").tobytes()
+    start_bits = np.zeros(total, dtype=np.uint8)
+    start_bits[starts] = 1
+    return header + np.packbits(start_bits).tobytes() + pack_fixed_bit(dict_ids, bits)
+
+
+def unpack_mv_fwd(buf: bytes, bits: int, num_docs: int, total_values: int):
+    """Inverse of :func:`mv_fwd_bytes` (FixedBitMVForwardIndexReader.java:66-141 for every doc): (offsets, dictIds)
+    with doc d's dictIds at dictIds[offsets[d]:offsets[d + 1]]. The sizes, the chunk offsets and the bitmap are
+    checked against each other (ValueError)."""
+    if num_docs == 0:
+        if total_values or len(buf):
+            raise ValueError("a segment without docs has an empty multi-value forward index")
+        return np.zeros(1, np.int32), np.zeros(0, np.int32)
+    if total_values < num_docs:
+        raise ValueError("fewer values than docs")
+    dpc = mv_docs_per_chunk(num_docs, total_values)
+    num_chunks = (num_docs + dpc - 1) // dpc
+    bm_off = 4 * num_chunks
+    raw_off = bm_off + (total_values + 7) // 8
+    size = raw_off + (total_values * bits + 7) // 8
+    if len(buf) != size:
+        raise ValueError(f"multi-value forward index of {len(buf)} bytes, expected {size}")
+    a = np.frombuffer(buf, dtype=np.uint8)
+    start_bits = np.unpackbits(a[bm_off:raw_off])[:total_values]
+    starts = np.nonzero(start_bits)[0]
+    if starts.size != num_docs or starts[0] != 0:
+        raise ValueError("the bitmap does not mark one start per doc from value 0")
+    header = np.frombuffer(buf, dtype=">i4", count=num_chunks).astype(np.int64)
+    if not np.array_equal(header, starts[::dpc]):
+        raise ValueError("the chunk offsets disagree with the bitmap")
+    ids = unpack_fixed_bit(bytes(a[raw_off:]), bits, total_values)
+    return np.r_[starts, total_values].astype(np.int32), ids
 
 
 # --------------------------------------------------------------------------- sorted fwd
@@ -518,9 +592,14 @@ class ColumnBuffers:
     dictionary: bytes = b""              # dictionary buffer (dict-encoded columns)
     inverted: Optional[bytes] = None     # bitmap inverted index buffer
     dict_values: Optional[np.ndarray] = None  # decoded dictionary (host convenience)
+    multi_value: bool = False            # isSingleValues = false: fwd is the FixedBitMVForwardIndexWriter file
+    total_values: int = 0                # totalNumberOfEntries
+    max_values: int = 0                  # maxNumberOfMultiValues
 
     @property
     def encoding(self) -> str:
+        if self.multi_value:
+            return "FIXED_BIT_MV"
         if not self.has_dictionary:
             return "RAW"
         return "SORTED" if self.is_sorted else "FIXED_BIT"
@@ -537,8 +616,24 @@ class SegmentBuffers:
 
 
 def build_column(name: str, values, stored_type: str, dictionary: bool = True, inverted: bool = False,
-                 detect_sorted: bool = True, raw_version: int = 4, compression: int = PASS_THROUGH) -> ColumnBuffers:
-    """Create one column's buffers the way SegmentColumnarIndexCreator would for an SV column."""
+                 detect_sorted: bool = True, raw_version: int = 4, compression: int = PASS_THROUGH,
+                 multi_value: bool = False) -> ColumnBuffers:
+    """Create one column's buffers the way SegmentColumnarIndexCreator would for an SV column, or with
+    multi_value=True (`values`: one array of values per doc, each with at least one) for a dictionary-encoded
+    MV column."""
+    if multi_value:
+        if not dictionary or inverted:
+            raise NotImplementedError("multi-value columns: dictionary-encoded, without an inverted index")
+        docs = [np.asarray(d, dtype=object if stored_type == STRING else _NP_LE[stored_type]) for d in values]
+        flat = np.concatenate(docs) if docs else np.zeros(0, dtype=object if stored_type == STRING else _NP_LE[stored_type])
+        dvals, ids = build_dictionary(flat, stored_type)
+        card = len(dvals)
+        bits = num_bits_per_value(card - 1)
+        lens = [len(d) for d in docs]
+        bounds = np.r_[0, np.cumsum(lens)].astype(np.int64)
+        fwd = mv_fwd_bytes([ids[bounds[i]:bounds[i + 1]] for i in range(len(docs))], bits)
+        return ColumnBuffers(name, stored_type, len(docs), True, False, card, bits, fwd,
+                             dictionary_bytes(dvals, stored_type), None, dvals, True, int(bounds[-1]), max(lens + [0]))
     vals = np.asarray(values, dtype=object if stored_type == STRING else _NP_LE[stored_type])
     n = int(vals.size)
     if not dictionary:
@@ -600,7 +695,8 @@ def load_segment_dir(path: str) -> SegmentBuffers:
     column metadata; index buffers from V1 per-index files (FilePerIndexDirectory: <col>.dict,
     <col>.sv.{sorted,unsorted,raw}.fwd, <col>.bitmap.inv) or from V3's single columns.psf sliced by
     index_map (SingleFileIndexDirectory: <col>.<index>.startOffset / .size, each index prefixed by an
-    8-byte magic marker). Single-value INT / LONG / FLOAT / DOUBLE / STRING columns; a raw column's
+    8-byte magic marker). Single-value INT / LONG / FLOAT / DOUBLE / STRING columns and dictionary-encoded
+    multi-value ones (isSingleValues = false: <col>.mv.fwd, totalNumberOfEntries, maxNumberOfMultiValues); a raw column's
     legacy raw-value inverted index is dropped (SegmentPreProcessor.removeLegacyRawValueInvertedIndexes)."""
     import os
     v3 = os.path.join(path, "v3")
@@ -635,9 +731,18 @@ def load_segment_dir(path: str) -> SegmentBuffers:
     out = {}
     for c in cols:
         m = {k[len("column.") + len(c) + 1:]: v for k, v in meta.items() if k.startswith(f"column.{c}.")}
-        if m.get("isSingleValues", "true") != "true":
-            raise NotImplementedError(f"multi-value column {c}")
         st = _TYPE_NAMES[m["dataType"]]
+        if m.get("isSingleValues", "true") != "true":
+            # (V1: <col>.mv.fwd, FilePerIndexDirectory; V3: the same forward_index entry as an SV column)
+            if m.get("hasDictionary", "true") != "true":
+                raise NotImplementedError(f"raw (no-dictionary) multi-value column {c}")
+            card = int(m.get("cardinality", "0"))
+            dic = index_bytes(c, "dictionary", ".dict")
+            out[c] = ColumnBuffers(c, st, num_docs, True, False, card, int(m.get("bitsPerElement", "0")),
+                                   index_bytes(c, "forward_index", ".mv.fwd") or b"", dic, None,
+                                   decode_dictionary(dic, st, card), True, int(m["totalNumberOfEntries"]),
+                                   int(m["maxNumberOfMultiValues"]))
+            continue
         has_dict = m.get("hasDictionary", "true") == "true"
         is_sorted = m.get("isSorted", "false") == "true"
         card = int(m.get("cardinality", "0"))
