@@ -319,6 +319,39 @@ typedef struct pinot_amd_key_transform_spec {
  * the query's identity: queries that differ only in it never share a prepared plan. */
 int pinot_amd_query_add_group_by_transform(pinot_amd_query* q, const char* column,
                                            const pinot_amd_key_transform_spec* spec);
+/* An arithmetic expression over single-value INT / LONG / FLOAT / DOUBLE columns (raw, fixed-bit dictionary or sorted,
+ * per segment) and numeric literals, as a postfix tree. Every node's value is a Java double: columns are read as
+ * transformToDoubleValuesSV reads them (LONG is (double) v), the result is DOUBLE. Evaluation, in this order
+ * (pinot-core/.../operator/transform/function/):
+ *   ADD (n >= 2)      acc = 0.0 + the literal arguments in order, then acc += each other argument in order
+ *                     (AdditionTransformFunction: plus(x, y) of two -0.0 is 0.0)
+ *   MULT (n >= 2)     acc = 1.0 * the literal arguments, then acc *= each other argument (MultiplicationTransformFunction)
+ *   SUB, DIV, MOD     first - second, first / second (IEEE: x / 0 = +-inf, 0 / 0 = NaN), Java % = fmod
+ *   ABS CEIL FLOOR SQRT SIGN   Math.abs / ceil / floor / sqrt / signum of one non-literal argument
+ *   LEAST, GREATEST (n >= 2)   a left fold of Math.min / Math.max (NaN propagates, -0.0 < 0.0)
+ * The device result is bit-identical to Java's (no fused multiply-add, no flushed denormals; every NaN is one value).
+ * num_args is read for the operator nodes, `column` for COLUMN, `literal` for LITERAL.
+ * *out_name is the name of a virtual single-value DOUBLE column of this query, owned by the query; it contains '$'.
+ * It is accepted wherever a raw DOUBLE column's name is: pinot_amd_query_add_predicate, _add_aggregation,
+ * _add_aggregation_param, _add_aggregation_filter_predicate, _add_group_by, _add_selection and
+ * _add_selection_order_by. Equal trees -- the same operators, columns and literal bits after the literal folding
+ * above -- get one name, and a segment one twin column per name: built on the device at the first query that needs it,
+ * kept staged beside the sources, counted in pinot_amd_segment_device_bytes. The name is part of the query wherever
+ * it is used, so queries that differ in a literal share no prepared plan.
+ * EINVAL here: more than 32 nodes or 8 distinct columns, a malformed postfix, an arity the list above does not
+ * allow, ABS .. SIGN of a literal, an expression without a column. EUNSUPPORTED here: a kind outside the enum (exp,
+ * ln, power, round, CASE, CAST ... have none: their libm / BigDecimal results are not bit-reproducible). From
+ * pinot_amd_execute: a STRING source EINVAL, a multi-value source EUNSUPPORTED. pinot_amd_query_add_group_by_transform
+ * and pinot_amd_query_set_group_key_values of an expression: EUNSUPPORTED.
+ * Expression twins (and the "$dict" twins GROUP BY derives from them) are bounded per device by
+ * PINOT_AMD_EXPR_TWIN_BYTES (default: 1/8 of the device's memory): building one beyond the budget first drops the
+ * least recently used twins no live result reads (with the idle prepared plans over their segments); when none can
+ * go the budget is exceeded -- no query fails because of it. */
+enum pinot_amd_xnode_kind { PINOT_AMD_X_COLUMN, PINOT_AMD_X_LITERAL, PINOT_AMD_X_ADD, PINOT_AMD_X_SUB, PINOT_AMD_X_MULT,
+                            PINOT_AMD_X_DIV, PINOT_AMD_X_MOD, PINOT_AMD_X_ABS, PINOT_AMD_X_CEIL, PINOT_AMD_X_FLOOR,
+                            PINOT_AMD_X_SQRT, PINOT_AMD_X_SIGN, PINOT_AMD_X_LEAST, PINOT_AMD_X_GREATEST };
+typedef struct pinot_amd_xnode { int32_t kind; int32_t num_args; const char* column; double literal; } pinot_amd_xnode;
+int pinot_amd_query_define_expression(pinot_amd_query* q, const pinot_amd_xnode* postfix, int32_t n, const char** out_name);
 /* Aggregation function (column NULL or "*" for COUNT(*)). Returns the aggregation index via out_index.
  * PINOT_AMD_AGG_DISTINCTCOUNT takes a column of any stored type, STRING included (EINVAL for NULL / "*").
  * Types above PINOT_AMD_AGG_DISTINCTCOUNT: EINVAL (pinot_amd_query_add_aggregation_param adds the value-set

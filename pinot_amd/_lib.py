@@ -54,6 +54,11 @@ class KeyTransformSpec(C.Structure):
     ]
 
 
+class XNode(C.Structure):
+    """pinot_amd_xnode: one node of an expression's postfix (pinot_amd_query_define_expression)."""
+    _fields_ = [("kind", C.c_int32), ("num_args", C.c_int32), ("column", C.c_char_p), ("literal", C.c_double)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/pinot_amd.h
 _P = C.c_void_p
 _PP = C.POINTER(C.c_void_p)
@@ -88,6 +93,7 @@ SIGNATURES = {
     "pinot_amd_query_add_predicate": (C.c_int, [_P, C.c_int32, C.POINTER(PredicateSpec), C.c_int32]),
     "pinot_amd_query_add_group_by": (C.c_int, [_P, C.c_char_p]),
     "pinot_amd_query_add_group_by_transform": (C.c_int, [_P, C.c_char_p, C.POINTER(KeyTransformSpec)]),
+    "pinot_amd_query_define_expression": (C.c_int, [_P, C.POINTER(XNode), C.c_int32, C.POINTER(C.c_char_p)]),
     "pinot_amd_query_add_aggregation": (C.c_int, [_P, C.c_int32, C.c_char_p, C.POINTER(C.c_int32)]),
     "pinot_amd_query_add_aggregation_param": (C.c_int, [_P, C.c_int32, C.c_char_p, C.c_double,
                                                         C.POINTER(C.c_int32)]),

@@ -29,6 +29,7 @@
 
 #include "../../include/pinot_amd.h"
 #include "device_types.h"
+#include "expr.h"
 #include "jit.h"
 #include "kernels.h"
 
@@ -107,6 +108,7 @@ static const std::set<std::string>& kept_knobs() {
       "PINOT_AMD_TOPK_BLOCKS",
       "PINOT_AMD_TOPK_LDS_ROWS",
       "PINOT_AMD_TOPK_SORT_MAX_BYTES",
+      "PINOT_AMD_EXPR_TWIN_BYTES",
   };
   return kept;
 }
@@ -1420,6 +1422,10 @@ struct pinot_amd_query {
   // identity, key caches, the value-set sub-queries' copies); twin name -> (source column, spec)
   struct KeyTransform { std::string column; DevKeyTransform tf; };
   std::map<std::string, KeyTransform> key_tf;
+  // arithmetic expressions (pinot_amd_query_define_expression): the virtual column's name -> its canonical tree. The
+  // name stands wherever a column's does (predicates, GROUP BY, aggregations, selection), so it is part of everything
+  // keyed by the query's text; PlanBuild::raw_keys gives every segment a raw DOUBLE twin under that name
+  std::map<std::string, ExprDef> exprs;
   // group-by column -> key space installed by the caller (the union of every server's dictionaries); shared,
   // immutable once installed (every plan of the query reads the same one, never a copy)
   std::map<std::string, std::shared_ptr<const MergedKeyColumn>> key_space;
@@ -1551,6 +1557,8 @@ int pinot_amd_query_add_group_by_transform(pinot_amd_query* q, const char* colum
   if (!q || !column || !*column || !spec) return fail(PINOT_AMD_EINVAL, "add_group_by_transform: bad arguments");
   if (q->group_by.size() >= (size_t)kMaxGroupCols)
     return fail(PINOT_AMD_EUNSUPPORTED, "add_group_by_transform: too many columns");
+  if (q->exprs.count(column))
+    return fail(PINOT_AMD_EUNSUPPORTED, "add_group_by_transform: GROUP BY transform of an expression (a DOUBLE value)");
   auto unit_ok = [](int32_t u) { return u >= PINOT_AMD_NANOSECONDS && u <= PINOT_AMD_DAYS; };
   if (spec->kind < PINOT_AMD_KEY_DATETRUNC || spec->kind > PINOT_AMD_KEY_DATETIMECONVERT)
     return fail(PINOT_AMD_EINVAL, "add_group_by_transform: bad kind %d", spec->kind);
@@ -1593,6 +1601,23 @@ int pinot_amd_query_add_group_by_transform(pinot_amd_query* q, const char* colum
   const std::string twin = std::string(column) + b;
   q->key_tf[twin] = {column, tf};
   q->group_by.push_back(twin);
+  return 0;
+}
+
+int pinot_amd_query_define_expression(pinot_amd_query* q, const pinot_amd_xnode* postfix, int32_t n,
+                                      const char** out_name) {
+  if (!q || !postfix || !out_name) return fail(PINOT_AMD_EINVAL, "define_expression: bad arguments");
+  if (n < 1 || n > kMaxExprNodes)
+    return fail(PINOT_AMD_EINVAL, "define_expression: %d nodes (1 to %d)", n, kMaxExprNodes);
+  std::vector<ExprNodeIn> in((size_t)n);
+  for (int32_t i = 0; i < n; ++i) in[(size_t)i] = {postfix[i].kind, postfix[i].num_args, postfix[i].column, postfix[i].literal};
+  ExprDef d;
+  std::string msg;
+  if (int v = expr_canonicalize(in.data(), n, &d, &msg))
+    return fail(v == XV_EUNSUPPORTED ? PINOT_AMD_EUNSUPPORTED : PINOT_AMD_EINVAL, "%s", msg.c_str());
+  const std::string name = d.name;
+  auto it = q->exprs.emplace(name, std::move(d)).first;  // (an equal tree defined before: the same entry)
+  *out_name = it->first.c_str();
   return 0;
 }
 
@@ -1657,6 +1682,9 @@ int pinot_amd_query_set_group_key_values(pinot_amd_query* q, const char* column,
                                          const char* const* h_values_s) {
   if (!q || !column || n < 0 || stored_type < T_INT || stored_type > T_STRING)
     return fail(PINOT_AMD_EINVAL, "set_group_key_values: bad arguments");
+  if (q->exprs.count(column))
+    return fail(PINOT_AMD_EUNSUPPORTED, "set_group_key_values: %s is an expression (its key space is the union over "
+                                        "the batch)", column);
   const bool plain = std::find(q->group_by.begin(), q->group_by.end(), column) != q->group_by.end();
   for (const auto& kt : q->key_tf)
     if (kt.first == column || (!plain && kt.second.column == column))
@@ -1857,6 +1885,9 @@ struct DistinctFold {
   ~DistinctFold();
 };
 
+struct pinot_amd_result;
+static void expr_twin_pin(pinot_amd_result* r, bool on);
+
 struct pinot_amd_result {
   std::unique_ptr<DistinctFold> dc;  // a DISTINCTCOUNT query's result (see DistinctFold)
   hipStream_t stream = nullptr;
@@ -1925,6 +1956,10 @@ struct pinot_amd_result {
   // prepared-plan cache (plan_cache_*): the identity this plan was built for, the segments it reads, its device bytes
   std::string plan_key;
   std::vector<uint64_t> plan_uids;
+  // expression twins the plan reads, (segment uid, twin name): pinned against eviction while the result is live
+  // (expr_twin_pin), released while the plan sits idle in the plan cache
+  std::vector<std::pair<uint64_t, std::string>> xtw;
+  bool xtw_pinned = false;
   size_t plan_bytes = 0;
   // segment-level group trim over the (key, segment) scan table of a hash plan (SegSelStage, launch_segsel): the
   // safe trim past the dense cap (keep = LIMIT) and the unsafe trim with minSegmentGroupTrimSize (keep =
@@ -2032,6 +2067,7 @@ struct pinot_amd_result {
   std::vector<int64_t> row_vals;                        // sel_nrows x sel_nout (fetch's key encoding)
   std::vector<std::vector<std::string>> row_strings;    // per selected STRING column: the kept rows' strings by id
   ~pinot_amd_result() {
+    expr_twin_pin(this, false);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
     if (ev_x) (void)hipEventDestroy(ev_x);
@@ -2164,6 +2200,7 @@ static pinot_amd_result* plan_cache_take(const std::string& key) {
   pinot_amd_result* r = it->second.r.release();
   g_plan_bytes -= r->plan_bytes;
   g_plans.erase(it);
+  expr_twin_pin(r, true);  // live again (its twins are there: dropping one drops the idle plans over its segment)
   return r;
 }
 
@@ -2183,6 +2220,7 @@ static bool plan_cache_put(pinot_amd_result* r) {
       evicted.push_back(std::move(lru->second.r));
       g_plans.erase(lru);
     }
+    expr_twin_pin(r, false);  // idle: its expression twins may go (and take this plan with them)
     PlanCacheEntry e;
     e.r.reset(r);
     e.used = ++g_plan_clock;
@@ -2901,6 +2939,242 @@ static int derive_mv_twin(pinot_amd_segment* s, const std::string& col, int op, 
   return pinot_amd_segment_add_column(s, &spec);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Expression twins (pinot_amd_query_define_expression)
+// ------------------------------------------------------------------------------------------------
+// Every segment a query with an expression reads gets a raw DOUBLE twin of the expression's per-doc value under the
+// expression's name, written by a generated kernel (expr.h: expr_kernel_source, compiled through the JIT cache per
+// (tree, sources' encodings / types / widths)) and installed without leaving the device. Literals make the space of
+// expressions unbounded, so the twins -- and the "$dict" twins GROUP BY derives from them -- are tallied per device
+// against PINOT_AMD_EXPR_TWIN_BYTES (default 1/8 of the device's memory: a policy, like the pool's and the plan
+// cache's): before a twin is built beyond the budget the least recently used twins that no live result pins are
+// dropped, with the idle prepared plans over their segments (plan_cache_drop_uid) and a bump of the segment's
+// generation. A plan pins its twins while its result is live (pinot_amd_result::xtw); nothing droppable: the budget
+// is exceeded, no query fails.
+struct ExprTwin {
+  pinot_amd_segment* seg = nullptr;
+  int dev = 0;
+  size_t bytes = 0;  // the twin, plus its "$dict" twin once a GROUP BY derived one
+  uint64_t used = 0;
+  int live = 0;  // results (executed, not destroyed) reading it
+};
+static thread_local double g_tl_expr_kernel_ms = 0;  // device time of the evaluators this thread launched
+static std::mutex g_xtw_mu;
+static std::map<std::pair<uint64_t, std::string>, ExprTwin> g_xtw;
+static std::map<int, size_t> g_xtw_bytes;
+static uint64_t g_xtw_clock = 0;
+
+static void expr_twin_pin(pinot_amd_result* r, bool on) {
+  if (r->xtw_pinned == on || r->xtw.empty()) return;
+  std::lock_guard<std::mutex> g(g_xtw_mu);
+  for (const auto& k : r->xtw) {
+    auto it = g_xtw.find(k);
+    if (it == g_xtw.end()) continue;  // (its segment was destroyed)
+    it->second.live += on ? 1 : -1;
+    if (on) it->second.used = ++g_xtw_clock;
+  }
+  r->xtw_pinned = on;
+}
+
+static size_t expr_twin_budget(int dev) {
+  if (const char* v = knob("PINOT_AMD_EXPR_TWIN_BYTES")) return (size_t)std::max(0ll, atoll(v));
+  static std::mutex mu;
+  static std::map<int, size_t> total;
+  std::lock_guard<std::mutex> g(mu);
+  auto it = total.find(dev);
+  if (it == total.end()) {
+    size_t t = 0;
+    if (hipDeviceTotalMem(&t, dev) != hipSuccess) t = (size_t)64 << 30;
+    it = total.emplace(dev, t / 8).first;
+  }
+  return it->second;
+}
+
+// removes column `name` of the segment: its bytes leave the accounting, its fingerprints the table
+static void drop_twin_column(pinot_amd_segment* s, const std::string& name) {
+  auto it = s->cols.find(name);
+  if (it == s->cols.end()) return;
+  Column& c = *it->second;
+  s->device_bytes -= (int64_t)(c.fwd.n + c.dict.n + c.inv.n + c.inv_conts.n + c.for_lo.n + c.for_hi.n);
+  {
+    std::lock_guard<std::mutex> g(g_print_mu);
+    for (const void* p : {c.fwd.p, c.for_lo.p, c.for_hi.p}) g_prints.erase(p);
+  }
+  s->cols.erase(it);
+}
+
+// room for `need` more twin bytes on the device: the least recently used unpinned twins go while the budget is
+// exceeded (never a twin of `keep_uid` named in `keep`: the running query's own)
+static void expr_twin_make_room(int dev, size_t need, const std::vector<std::pair<uint64_t, std::string>>& keep) {
+  const size_t budget = expr_twin_budget(dev);
+  for (;;) {
+    std::pair<uint64_t, std::string> victim;
+    pinot_amd_segment* seg = nullptr;
+    {
+      std::lock_guard<std::mutex> g(g_xtw_mu);
+      if (g_xtw_bytes[dev] + need <= budget) return;
+      auto lru = g_xtw.end();
+      for (auto it = g_xtw.begin(); it != g_xtw.end(); ++it) {
+        if (it->second.dev != dev || it->second.live > 0) continue;
+        if (std::find(keep.begin(), keep.end(), it->first) != keep.end()) continue;
+        if (lru == g_xtw.end() || it->second.used < lru->second.used) lru = it;
+      }
+      if (lru == g_xtw.end()) return;  // nothing droppable: over the budget
+      victim = lru->first;
+      seg = lru->second.seg;
+      g_xtw_bytes[dev] -= lru->second.bytes;
+      g_xtw.erase(lru);
+    }
+    plan_cache_drop_uid(victim.first);  // the idle plans over the segment (one of them may read the twin)
+    (void)hipDeviceSynchronize();       // (nothing in flight reads it: no live result does)
+    drop_twin_column(seg, victim.second);
+    drop_twin_column(seg, victim.second + "$dict");
+    {
+      std::lock_guard<std::mutex> g(g_leaf_mu);
+      seg->leaf_cache.clear();
+    }
+    ++seg->gen;
+  }
+}
+
+// a destroyed segment's twins leave the tally
+static void expr_twin_forget_segment(uint64_t uid) {
+  std::lock_guard<std::mutex> g(g_xtw_mu);
+  for (auto it = g_xtw.begin(); it != g_xtw.end();) {
+    if (it->first.first == uid) {
+      g_xtw_bytes[it->second.dev] -= it->second.bytes;
+      it = g_xtw.erase(it);
+    } else {
+      ++it;
+    }
+  }
+}
+
+// the "$dict" twin GROUP BY derived from expression twin `name` counts with it
+static void expr_twin_note_dict(pinot_amd_segment* s, const std::string& name) {
+  auto c = s->cols.find(name + "$dict");
+  if (c == s->cols.end()) return;
+  std::lock_guard<std::mutex> g(g_xtw_mu);
+  auto it = g_xtw.find({s->uid, name});
+  if (it == g_xtw.end()) return;
+  const size_t own = s->cols.at(name)->fwd.n;
+  const size_t with = own + c->second->fwd.n + c->second->dict.n;
+  if (it->second.bytes >= with) return;
+  g_xtw_bytes[it->second.dev] += with - it->second.bytes;
+  it->second.bytes = with;
+}
+
+// What an expression may not read, over the whole batch and before anything is built (a refusal stages nothing).
+static int check_expr_sources(const ExprDef& e, const std::vector<pinot_amd_segment*>& segs) {
+  for (const std::string& col : e.cols) {
+    int type = -1;
+    for (auto* s : segs) {
+      auto it = s->cols.find(col);
+      if (it == s->cols.end()) return fail(PINOT_AMD_EINVAL, "segment %s has no column %s", s->name.c_str(), col.c_str());
+      const Column& c = *it->second;
+      if (c.mv) return fail(PINOT_AMD_EUNSUPPORTED, "multi-value column %s in an expression", col.c_str());
+      if (c.type == T_STRING) return fail(PINOT_AMD_EINVAL, "STRING column %s in an expression", col.c_str());
+      if (type >= 0 && c.type != type)
+        return fail(PINOT_AMD_EINVAL, "column %s has different types across segments", col.c_str());
+      type = c.type;
+      if (c.enc != ENC_RAW && s->num_docs > 0 && c.card < 1)
+        return fail(PINOT_AMD_EINVAL, "column %s: empty dictionary", col.c_str());
+    }
+  }
+  return 0;
+}
+
+// The twin of expression `e` in segment `s` (built unless it is there), pinned for result `r`.
+static int derive_expr_twin(pinot_amd_segment* s, const ExprDef& e, pinot_amd_result* r) {
+  const std::pair<uint64_t, std::string> key{s->uid, e.name};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (s->cols.count(e.name)) {
+    std::lock_guard<std::mutex> g(g_xtw_mu);
+    auto it = g_xtw.find(key);
+    if (it != g_xtw.end() && std::find(r->xtw.begin(), r->xtw.end(), key) == r->xtw.end()) {
+      it->second.used = ++g_xtw_clock;
+      ++it->second.live;
+      r->xtw.push_back(key);
+      r->xtw_pinned = true;
+    }
+    return 0;
+  }
+  const int64_t nd = s->num_docs;
+  DevBuf out;
+  const size_t bytes = (size_t)nd * 8 + kPadBytes;
+  expr_twin_make_room(dev, bytes, r->xtw);
+  if (int rc = out.raw_alloc(bytes)) return rc;
+  HIP_OK(hipMemset(out.p, 0, out.n));
+  if (nd > 0) {
+    std::vector<ExprSrcShape> shapes;
+    std::vector<const Column*> cols;
+    for (const std::string& col : e.cols) {
+      const Column& c = *s->cols.at(col);
+      shapes.push_back({c.enc, c.type, c.enc == ENC_FIXED_BIT ? c.bits : 0});
+      cols.push_back(&c);
+    }
+    std::string err;
+    JitKernel* k = jit_get_source(expr_kernel_key(e, shapes), expr_kernel_source(e, shapes), "pinot_expr_eval", &err);
+    if (!k) return fail(PINOT_AMD_EUNSUPPORTED, "expression %s: %s", e.name.c_str(), err.c_str());
+    std::vector<const void*> ptrs(2 * cols.size());
+    std::vector<int32_t> cards(cols.size());
+    std::vector<void*> args;
+    for (size_t i = 0; i < cols.size(); ++i) {
+      ptrs[2 * i] = cols[i]->fwd.p;
+      ptrs[2 * i + 1] = cols[i]->dict.p;
+      cards[i] = cols[i]->card;
+      args.push_back(&ptrs[2 * i]);
+      args.push_back(&ptrs[2 * i + 1]);
+      args.push_back(&cards[i]);
+    }
+    void* outp = out.p;
+    long long num_docs = nd, tiles = (nd + kTileDocs - 1) / kTileDocs;
+    args.push_back(&outp);
+    args.push_back(&num_docs);
+    args.push_back(&tiles);
+    const unsigned grid = (unsigned)std::min<long long>(tiles, 8192);
+    // the evaluator's time, launch to completion on the host's clock, reported in plan_timing (expr_kernel)
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_OK(hipModuleLaunchKernel(k->fn, grid, 1, 1, kBlock, 1, 1, 0, nullptr, args.data(), nullptr));
+    HIP_OK(hipStreamSynchronize(nullptr));
+    g_tl_expr_kernel_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  // installed as a raw DOUBLE column by its last step: the staged layout (big-endian values, zero padding), its
+  // fingerprint, the segment's byte count and generation -- what pinot_amd_segment_add_column does for host bytes
+  auto c = std::make_unique<Column>();
+  c->name = e.name;
+  c->type = T_DOUBLE;
+  c->enc = ENC_RAW;
+  StagedPrint sp{out.n, 0};
+  if (int rc = device_fingerprint(out.p, sp.bytes, &sp.print)) return rc;
+  c->fwd.p = out.p;
+  c->fwd.n = out.n;
+  c->fwd.bsz = out.bsz;
+  out.p = nullptr;
+  out.n = out.bsz = 0;
+  {
+    std::lock_guard<std::mutex> g(g_print_mu);
+    g_prints[c->fwd.p] = sp;
+  }
+  ++s->gen;
+  s->device_bytes += (int64_t)c->fwd.n;
+  const size_t held = c->fwd.n;
+  s->cols[e.name] = std::move(c);
+  std::lock_guard<std::mutex> g(g_xtw_mu);
+  ExprTwin t;
+  t.seg = s;
+  t.dev = dev;
+  t.bytes = held;
+  t.used = ++g_xtw_clock;
+  t.live = 1;
+  g_xtw[key] = t;
+  g_xtw_bytes[dev] += held;
+  r->xtw.push_back(key);
+  r->xtw_pinned = true;
+  return 0;
+}
+
 static int build_merged_keys_uncached(const std::vector<pinot_amd_segment*>& segs, const std::string& col,
                                       MergedKeyColumn* out);
 
@@ -2930,6 +3204,7 @@ static uint64_t g_cache_clock = 0;
 
 static void drop_segment_caches(uint64_t uid) {
   plan_cache_drop_uid(uid);
+  expr_twin_forget_segment(uid);
   std::lock_guard<std::mutex> g(g_keys_mu);
   for (auto it = g_keys_cache.begin(); it != g_keys_cache.end();) {
     if (std::find(it->second.uids.begin(), it->second.uids.end(), uid) != it->second.uids.end()) {
@@ -3775,6 +4050,7 @@ struct PlanBuild {
   bool filter_only = false;
   bool sel = false;  // a selection query: the top-K scan instead of an aggregation
   pinot_amd_result* r = nullptr;
+  bool restaged = false;  // raw_keys staged an expression twin (the segments' generations moved)
   // the effective query (raw_keys)
   pinot_amd_query filter_q;  // FilterPlanNode only: no projection, no aggregation
   pinot_amd_query raw_gb_q;  // group-by columns redirected to the derived dictionary of raw columns
@@ -3867,6 +4143,34 @@ int PlanBuild::raw_keys() {
     sel_q.sel_order.clear();
     Qp = &sel_q;
   }
+  // expressions (pinot_amd_query_define_expression): every one the effective query names gets its raw DOUBLE twin
+  // in every segment that lacks it; the sources' types over the whole batch first (a refusal stages nothing). From
+  // here on the name is an ordinary column's
+  if (!qq->exprs.empty()) {
+    std::vector<const ExprDef*> used;
+    auto note = [&](const std::string& name) {
+      auto it = qq->exprs.find(name);
+      if (it != qq->exprs.end() && std::find(used.begin(), used.end(), &it->second) == used.end()) used.push_back(&it->second);
+    };
+    for (const PredSpec& p : Qp->preds) note(p.column);
+    for (const auto& f : Qp->agg_filter)
+      for (const PredSpec& p : f) note(p.column);
+    for (const std::string& g : Qp->group_by) note(g);
+    for (const AggSpec& a : Qp->aggs) {
+      note(a.column);
+      note(a.column2);
+    }
+    for (const std::string& c : Qp->sel_cols) note(c);
+    for (const auto& o : Qp->sel_order) note(o.column);
+    for (const ExprDef* e : used)
+      if (int rc = check_expr_sources(*e, segs)) return rc;
+    for (const ExprDef* e : used)
+      for (auto* s : segs) {
+        const uint64_t gen0 = s->gen;
+        if (int rc = derive_expr_twin(s, *e, r)) return rc;
+        restaged |= s->gen != gen0;
+      }
+  }
   for (size_t j = 0; j < Qp->group_by.size(); ++j) {
     const std::string g = Qp->group_by[j];  // a copy: the redirect below rewrites Qp->group_by[j]
     auto kt = Qp->key_tf.find(g);
@@ -3895,8 +4199,10 @@ int PlanBuild::raw_keys() {
     if (nraw == 0) continue;
     if (nraw != n) return fail(PINOT_AMD_EUNSUPPORTED, "GROUP BY column %s is raw in some segments only", g.c_str());
     if (Qp != &raw_gb_q) { raw_gb_q = *Qp; Qp = &raw_gb_q; }
-    for (auto* s : segs)
+    for (auto* s : segs) {
       if (int rc = derive_raw_group_dictionary(s, g, &raw_gb_q.group_by[j])) return rc;
+      if (qq->exprs.count(g)) expr_twin_note_dict(s, g);  // (counts against the expression twins' budget)
+    }
   }
   // the *MV aggregations read the twins of their column's per-doc count / sum / min / max (check_mv_query has
   // refused what cannot run: from here only the twins' own staging can fail). AVGMV: the sum's twin, then the
@@ -4100,6 +4406,7 @@ int PlanBuild::probe_matched() {
   if (todo.empty()) return 0;
   pinot_amd_query fq;
   fq.preds = Q.preds;
+  fq.exprs = qq->exprs;
   pinot_amd_result* fr = nullptr;
   if (int rc = execute_impl(&fq, todo.data(), (int32_t)todo.size(), stream, true, &fr)) return rc;
   std::unique_ptr<pinot_amd_result> hold(fr);
@@ -6037,11 +6344,17 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
   b.filter_only = filter_only;
   b.sel = sel;
   b.r = r;
+  g_tl_expr_kernel_ms = 0;
   if (int rc = b.raw_keys()) return rc;
   // (twins staged for the *MV aggregations bumped their segments' generations: the plan is kept under the identity
   // the re-issued query will compute)
-  if (b.Qp == &b.mv_q) r->plan_key = plan_identity(*qq, b.segs, filter_only);
+  if (b.Qp == &b.mv_q || b.restaged) r->plan_key = plan_identity(*qq, b.segs, filter_only);
   clk.mark("raw_keys");
+  if (g_tl_expr_kernel_ms > 0) {  // of which: the expression evaluators on the device
+    char tb[48];
+    snprintf(tb, sizeof(tb), ";expr_kernel=%.4f", g_tl_expr_kernel_ms);
+    r->plan_timing += tb;
+  }
   if (int rc = b.lanes()) return rc;
   if (int rc = b.leaves()) return rc;
   clk.mark("leaves");

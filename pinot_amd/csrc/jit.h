@@ -248,5 +248,10 @@ std::string jit_generate(const JitPlan& p);
 std::string jit_full_source(const JitPlan& p);
 // compiled, loaded kernel for the plan's shape (cached); nullptr + *err when unavailable
 JitKernel* jit_get(const JitPlan& p, std::string* err);
+// a kernel generated outside the scan generator (the expression evaluators, expr.h): `src` compiled with the same
+// options, cached in the process under `key` and on disk by its text; JitKernel::fn is `entry`
+JitKernel* jit_get_source(const std::string& key, const std::string& src, const char* entry, std::string* err);
+// hipRTC compile of a source text to a code object (0: done; the log either way)
+int jit_compile(const std::string& src, std::vector<char>* code, std::string* log);
 
 }  // namespace pamd

@@ -199,6 +199,7 @@ def merge_result(result, scratch=None, group=None, stream=None, gather_max_bytes
     import torch
     import torch.distributed as dist
     _refuse_filtered_aggregations(getattr(result, "qc", None))
+    _refuse_expressions(getattr(result, "qc", None))
     _refuse_multi_value(getattr(result, "qc", None), result)
     cur = torch.cuda.current_stream() if torch.cuda.is_available() else None
     if stream is not None and cur is not None:
@@ -367,6 +368,7 @@ def merge_groups(qc, groups: dict, group=None) -> dict:
     import torch.distributed as dist
     from .query import merge_partial
     _refuse_filtered_aggregations(qc)
+    _refuse_expressions(qc)
     _refuse_multi_value(qc)
     world = dist.get_world_size(group)
     parts = [None] * world
@@ -407,6 +409,13 @@ def _refuse_filtered_aggregations(qc) -> None:
         raise ValueError("filtered aggregations (FILTER (WHERE ...)) are not covered by the cross-rank merge")
 
 
+def _refuse_expressions(qc) -> None:
+    """Arithmetic expressions run on one GPU: an expression has no installable key space
+    (pinot_amd_query_set_group_key_values: EUNSUPPORTED) and no tested cross-rank merge."""
+    if qc is not None and getattr(qc, "expressions", None) is not None and qc.expressions():
+        raise ValueError(f"arithmetic expressions ({', '.join(qc.expressions())}) are not covered by the cross-rank merge")
+
+
 def _refuse_multi_value(qc, result=None) -> None:
     """Multi-value columns run on one GPU: a query with an *MV aggregation or a predicate on an MV column has no
     tested cross-rank merge."""
@@ -434,6 +443,7 @@ def key_columns(qc) -> list:
     from .query import VALUE_SET_FUNCS
     cols = list(qc.group_by)
     _refuse_key_transforms(cols)
+    _refuse_expressions(qc)
     for a in qc.aggregations:
         if a.func in VALUE_SET_FUNCS and a.column not in cols:
             cols.append(a.column)

@@ -26,10 +26,11 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import ColumnSpec, KeyTransformSpec, PredicateSpec, check, lib
+from ._lib import ColumnSpec, KeyTransformSpec, PredicateSpec, XNode, check, lib
 from .query import (KEY_TRANSFORMS, MV_FUNCS, TIME_UNITS, TRUNC_UNITS, VALUE_SET_FUNCS, DistinctSize, FinalValue, JavaDouble,
-                    QueryContext, filter_text, fold_distinct_count, hists_from_csr, key_transform, parse_sql, reduce_rows,
-                    server_table, sets_from_csr, split_distinct_count, to_cnf)
+                    QueryContext, expr_columns, expr_postfix, expression, filter_text, fold_distinct_count,
+                    hists_from_csr, key_transform, parse_sql, reduce_rows, server_table, sets_from_csr,
+                    split_distinct_count, to_cnf)
 from .segment import ColumnBuffers, SegmentBuffers, DOUBLE, FLOAT, INT, LONG, STRING
 
 TYPE_CODE = {INT: 0, LONG: 1, FLOAT: 2, DOUBLE: 3, STRING: 4}
@@ -154,9 +155,55 @@ def _coerce(value, stored_type: str):
     return float(value)
 
 
-def _predicate_spec(pred, column: ColumnBuffers, use_inverted: bool, keep: list) -> PredicateSpec:
+class _ExprColumn:
+    """What the engine reads of a column, for an expression's virtual column: a single-value DOUBLE without indexes."""
+    stored_type = DOUBLE
+    inverted = None
+    multi_value = False
+
+    def __init__(self, name: str):
+        self.name = name
+
+
+class _QueryNames:
+    """The columns of one library query by the names its calls take: a plain column is itself, an arithmetic
+    expression (query.expression) is defined once per query (pinot_amd_query_define_expression) and stands under the
+    name the library returned."""
+
+    def __init__(self, qh, first: ImmutableSegment):
+        self._qh, self._first, self._defined = qh, first, {}
+
+    def column(self, text: str):
+        """The column's buffers (an _ExprColumn for an expression), None when the segment has no such column."""
+        e = expression(text)
+        if e is None:
+            return self._first.columns.get(text)
+        for c in expr_columns(e):
+            if c not in self._first.columns:
+                raise _lib.PinotAmdError(f"unknown column {c!r} in segment {self._first.name} (expression {text})")
+        return _ExprColumn(text)
+
+    def abi(self, text: str) -> bytes:
+        e = expression(text)
+        if e is None:
+            return text.encode()
+        name = self._defined.get(text)
+        if name is None:
+            rows = expr_postfix(e)
+            nodes = (XNode * len(rows))()
+            for n, (kind, nargs, col, lit) in zip(nodes, rows):
+                n.kind, n.num_args, n.column, n.literal = kind, nargs, (col.encode() if col is not None else None), lit
+            out = C.c_char_p()
+            check(lib().pinot_amd_query_define_expression(self._qh, nodes, len(rows), C.byref(out)),
+                  f"define_expression({text})")
+            name = self._defined[text] = out.value
+        return name
+
+
+def _predicate_spec(pred, column, use_inverted: bool, keep: list, abi_name: Optional[bytes] = None) -> PredicateSpec:
     s = PredicateSpec()
-    s.column = pred.column.encode()
+    s.column = abi_name if abi_name is not None else pred.column.encode()
+    keep.append(s.column)
     s.type = PRED_CODE[pred.type]
     st = column.stored_type
     s.use_inverted_index = 1 if (use_inverted and column.inverted is not None and pred.type != "RANGE") else 0
@@ -651,7 +698,7 @@ class ServerQueryExecutor:
         import torch
         qc = parse_sql(query) if isinstance(query, str) else query
         L = lib()
-        qh = self._compile(qc, segments)
+        qh, _ = self._compile(qc, segments)
         try:
             arr = (C.c_void_p * len(segments))(*[s.handle.value for s in segments])
             rh = C.c_void_p()
@@ -680,24 +727,28 @@ class ServerQueryExecutor:
         qh = C.c_void_p()
         check(L.pinot_amd_query_create(C.byref(qh)), "query_create")
         keep: list = []
+        names = _QueryNames(qh, first)
         try:
             for ci, clause in enumerate(qc.cnf):
                 for pred, neg in clause:
-                    col = first.columns.get(pred.column)
+                    col = names.column(pred.column)
                     if col is None:
                         raise _lib.PinotAmdError(f"unknown column {pred.column!r} in segment {first.name}")
-                    spec = _predicate_spec(pred, col, self.use_inverted_index, keep)
+                    spec = _predicate_spec(pred, col, self.use_inverted_index, keep, names.abi(pred.column))
                     check(L.pinot_amd_query_add_predicate(qh, ci, C.byref(spec), 1 if neg else 0), "add_predicate")
         except Exception:
             L.pinot_amd_query_destroy(qh)
             raise
-        return qh
+        return qh, names
 
     def execute(self, query, segments: Sequence[ImmutableSegment], stream=None, key_space=None):
         """Run a query over HBM-resident segments. key_space (optional): group-by column -> the values of
         its global key space (dist.global_key_space: the union of every rank's dictionaries), so that
         every rank's dense group table indexes the same groups."""
         qc = parse_sql(query) if isinstance(query, str) else query
+        if key_space is not None and qc.expressions():
+            raise ValueError(f"a query with arithmetic expressions ({', '.join(qc.expressions())}) takes no key_space: "
+                             "the cross-rank merge does not cover it")
         if qc.has_filtered_aggregations():
             if key_space is not None:
                 raise _lib.PinotAmdError("a query with filtered aggregations (FILTER (WHERE ...)) takes no key_space: the "
@@ -742,22 +793,24 @@ class ServerQueryExecutor:
         columns = qc.select_list(first)
         if not columns:
             raise ValueError("a selection query needs a column")
-        for c in columns + [c for c, _ in qc.order_by]:
-            if c not in first.columns:
-                raise _lib.PinotAmdError(f"unknown column {c!r} in segment {first.name}")
-        qh = self._compile(qc, segments)
+        qh, names = self._compile(qc, segments)
         try:
+            cbs = {}
+            for c in columns + [c for c, _ in qc.order_by]:
+                cbs[c] = names.column(c)
+                if cbs[c] is None:
+                    raise _lib.PinotAmdError(f"unknown column {c!r} in segment {first.name}")
             for c in columns:
-                check(L.pinot_amd_query_add_selection(qh, c.encode(), None), "add_selection")
+                check(L.pinot_amd_query_add_selection(qh, names.abi(c), None), "add_selection")
             for c, asc in qc.order_by:
-                check(L.pinot_amd_query_add_selection_order_by(qh, c.encode(), 1 if asc else 0), "add_selection_order_by")
+                check(L.pinot_amd_query_add_selection_order_by(qh, names.abi(c), 1 if asc else 0), "add_selection_order_by")
             check(L.pinot_amd_query_set_selection_limit(qh, qc.limit, qc.offset), "set_selection_limit")
             arr = (C.c_void_p * len(segments))(*[s.handle.value for s in segments])
             rh = C.c_void_p()
             check(L.pinot_amd_execute(qh, arr, len(segments), _stream_handle(stream), C.byref(rh)), "execute")
         finally:
             L.pinot_amd_query_destroy(qh)
-        return SelectionResult(rh, qc, columns, [first.columns[c].stored_type for c in columns])
+        return SelectionResult(rh, qc, columns, [cbs[c].stored_type for c in columns])
 
     @staticmethod
     def _set_key_space(qh, column: str, stored_type: str, values) -> None:
@@ -782,13 +835,14 @@ class ServerQueryExecutor:
         qh = C.c_void_p()
         check(L.pinot_amd_query_create(C.byref(qh)), "query_create")
         keep: list = []
+        names = _QueryNames(qh, first)
         try:
             for ci, clause in enumerate(qc.cnf):
                 for pred, neg in clause:
-                    col = first.columns.get(pred.column)
+                    col = names.column(pred.column)
                     if col is None:
                         raise _lib.PinotAmdError(f"unknown column {pred.column!r} in segment {first.name}")
-                    spec = _predicate_spec(pred, col, self.use_inverted_index, keep)
+                    spec = _predicate_spec(pred, col, self.use_inverted_index, keep, names.abi(pred.column))
                     check(L.pinot_amd_query_add_predicate(qh, ci, C.byref(spec), 1 if neg else 0), "add_predicate")
             for g in qc.group_by:
                 kt = key_transform(g)
@@ -800,7 +854,7 @@ class ServerQueryExecutor:
                     check(L.pinot_amd_query_add_group_by_transform(qh, kt.column.encode(), C.byref(spec)),
                           f"add_group_by_transform({g})")
                     continue
-                check(L.pinot_amd_query_add_group_by(qh, g.encode()), "add_group_by")
+                check(L.pinot_amd_query_add_group_by(qh, names.abi(g)), "add_group_by")
                 if key_space is not None and g in key_space:
                     self._set_key_space(qh, g, first.columns[g].stored_type, key_space[g])
             check(L.pinot_amd_query_set_num_groups_limit(qh, qc.num_groups_limit), "set_num_groups_limit")
@@ -824,15 +878,16 @@ class ServerQueryExecutor:
                 if key in native:
                     return native.index(key)
                 idx = C.c_int32()
+                abi_col = column.encode() if (expr is not None or column == "*") else names.abi(column)
                 if func in MV_FUNCS:  # the multi-value functions' entry point
                     check(L.pinot_amd_query_add_aggregation_mv(qh, AGG_CODE[func], column.encode(), C.byref(idx)),
                           f"add_aggregation_mv({func})")
                 elif AGG_CODE[func] > AGG_CODE["DISTINCTCOUNT"]:  # the functions with a literal argument's entry point
-                    check(L.pinot_amd_query_add_aggregation_param(qh, AGG_CODE[func], column.encode(),
+                    check(L.pinot_amd_query_add_aggregation_param(qh, AGG_CODE[func], abi_col,
                                                                   0.0 if param is None else param, C.byref(idx)),
                           f"add_aggregation_param({func})")
                 elif expr is None:
-                    check(L.pinot_amd_query_add_aggregation(qh, AGG_CODE[func], column.encode(), C.byref(idx)),
+                    check(L.pinot_amd_query_add_aggregation(qh, AGG_CODE[func], abi_col, C.byref(idx)),
                           f"add_aggregation({func})")
                 else:
                     check(L.pinot_amd_query_add_aggregation_expr(qh, AGG_CODE[func], EXPR_CODE[expr[0]],
@@ -840,10 +895,10 @@ class ServerQueryExecutor:
                           f"add_aggregation_expr({func} {column})")
                 for ci, clause in enumerate(to_cnf(filt)):
                     for pred, neg in clause:
-                        col = first.columns.get(pred.column)
+                        col = names.column(pred.column)
                         if col is None:
                             raise _lib.PinotAmdError(f"unknown column {pred.column!r} in segment {first.name}")
-                        spec = _predicate_spec(pred, col, self.use_inverted_index, keep)
+                        spec = _predicate_spec(pred, col, self.use_inverted_index, keep, names.abi(pred.column))
                         check(L.pinot_amd_query_add_aggregation_filter_predicate(qh, idx.value, ci, C.byref(spec),
                                                                                  1 if neg else 0),
                               "add_aggregation_filter_predicate")
@@ -855,12 +910,12 @@ class ServerQueryExecutor:
                     # (with FILTER: the sum and the count of the aggregation's lane)
                     agg_slots.append(("avg", add("SUM", a.column, a.expr, None, a.filter), add("COUNT", "*", None, None, a.filter)))
                 elif a.func == "DISTINCTCOUNT":  # the library folds the value sets (distinct_count="native")
-                    col = first.columns.get(a.column)
+                    col = names.column(a.column)
                     if col is None:
                         raise _lib.PinotAmdError(f"unknown column {a.column!r} in segment {first.name}")
                     agg_slots.append(("distinct", add("DISTINCTCOUNT", a.column, None, None, a.filter), col.stored_type))
                 elif a.func in VALUE_SET_FUNCS:    # PERCENTILE / DISTINCTSUM / DISTINCTAVG, likewise
-                    col = first.columns.get(a.column)
+                    col = names.column(a.column)
                     if col is None:
                         raise _lib.PinotAmdError(f"unknown column {a.column!r} in segment {first.name}")
                     agg_slots.append(("hist" if a.func == "PERCENTILE" else "dset",
@@ -887,7 +942,8 @@ class ServerQueryExecutor:
             check(L.pinot_amd_execute(qh, arr, len(segments), _stream_handle(stream), C.byref(rh)), "execute")
         finally:
             L.pinot_amd_query_destroy(qh)
-        key_types = [LONG if key_transform(g) is not None else first.columns[g].stored_type for g in qc.group_by]
+        key_types = [LONG if key_transform(g) is not None else DOUBLE if expression(g) is not None
+                     else first.columns[g].stored_type for g in qc.group_by]
         res = QueryResult(rh, qc, agg_slots, key_types)
         res._native_aggs = native
         # the multi-value columns the query filters on (dist.merge_result refuses such a result)

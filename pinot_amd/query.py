@@ -215,7 +215,10 @@ class Aggregation:
     def columns(self) -> Tuple[str, ...]:
         if self.column == "*":
             return ()
-        return (self.expr[1], self.expr[2]) if self.expr else (self.column,)
+        if self.expr:
+            return (self.expr[1], self.expr[2])
+        e = expression(self.column)
+        return tuple(expr_columns(e)) if e is not None else (self.column,)
 
 
 TIME_UNITS = ("NANOSECONDS", "MICROSECONDS", "MILLISECONDS", "SECONDS", "MINUTES", "HOURS", "DAYS")  # TimeUnit
@@ -341,6 +344,148 @@ def _key_transform(text: str) -> Optional[KeyTransform]:
     return kt
 
 
+# ------------------------------------------------------------------------------ arithmetic expressions
+# pinot_amd_xnode_kind, and the reference's function names (TransformFunctionType: ADD("add", "plus"), ... -- a call
+# keeps the name it was written with, lower case and without underscores; an operator is plus / minus / times /
+# divide / mod, CalciteSqlParser's canonical SqlKind names)
+X_COLUMN, X_LITERAL, X_ADD, X_SUB, X_MULT, X_DIV, X_MOD, X_ABS, X_CEIL, X_FLOOR, X_SQRT, X_SIGN, X_LEAST, X_GREATEST = range(14)
+ARITH_FUNCS = {"add": X_ADD, "plus": X_ADD, "sub": X_SUB, "minus": X_SUB, "mult": X_MULT, "times": X_MULT,
+               "div": X_DIV, "divide": X_DIV, "mod": X_MOD, "abs": X_ABS, "ceil": X_CEIL, "ceiling": X_CEIL,
+               "floor": X_FLOOR, "sqrt": X_SQRT, "sign": X_SIGN, "least": X_LEAST, "greatest": X_GREATEST}
+ARITH_OPS = {"+": "plus", "-": "minus", "*": "times", "/": "divide", "%": "mod"}
+# functions whose libm / BigDecimal results are not bit-reproducible on the device: refused by name
+UNSUPPORTED_FUNCS = ("exp", "ln", "log", "log2", "log10", "power", "pow", "round", "rounddecimal", "truncate", "sin",
+                     "cos", "tan", "asin", "acos", "atan", "atan2", "sinh", "cosh", "tanh", "cot", "degrees", "radians",
+                     "cbrt", "case", "cast")
+
+
+def java_double_text(x: float) -> str:
+    """Double.toString: decimal for 1e-3 <= |x| < 1e7, else computerised scientific notation (1.0E10)."""
+    x = float(x)
+    if math.isnan(x):
+        return "NaN"
+    if math.isinf(x):
+        return "Infinity" if x > 0 else "-Infinity"
+    if x == 0.0 or 1e-3 <= abs(x) < 1e7:
+        return repr(x)
+    mant, exp = f"{x!r}".lower().split("e") if "e" in repr(x).lower() else (None, None)
+    if mant is None:  # repr printed it in positional notation: normalise the digits
+        digits, e10 = f"{x:.17e}".split("e")
+        for prec in range(0, 18):  # the shortest digits that read back as x
+            cand = f"{x:.{prec}e}"
+            if float(cand) == x:
+                digits, e10 = cand.split("e")
+                break
+        mant, exp = digits, e10
+    if "." not in mant:
+        mant += ".0"
+    return f"{mant}E{int(exp)}"
+
+
+def literal_text(v) -> str:
+    """LiteralContext.toString without its quotes: an integral literal as an int / long, anything else as a double."""
+    return str(v) if isinstance(v, int) else java_double_text(v)
+
+
+def expr_text(e) -> str:
+    """ExpressionContext.toString of an expression tree: ('col', name) | ('lit', int or float) |
+    ('fn', name, [args]) -> times(times(a,b),'1.07')."""
+    if e[0] == "col":
+        return e[1]
+    if e[0] == "lit":
+        return f"'{literal_text(e[1])}'"
+    if e[0] == "cast":
+        raise ValueError("CAST in an expression is not supported")
+    return f"{e[1]}({','.join(expr_text(a) for a in e[2])})"
+
+
+def expr_columns(e) -> List[str]:
+    """The distinct columns of an expression tree, in first-use order."""
+    out: List[str] = []
+
+    def walk(n):
+        if n[0] == "col":
+            if n[1] not in out:
+                out.append(n[1])
+        elif n[0] == "fn":
+            for a in n[2]:
+                walk(a)
+    walk(e)
+    return out
+
+
+def expr_postfix(e) -> List[Tuple[int, int, Optional[str], float]]:
+    """pinot_amd_xnode rows (kind, num_args, column, literal) of an expression tree, in postfix."""
+    out = []
+
+    def walk(n):
+        if n[0] == "col":
+            out.append((X_COLUMN, 0, n[1], 0.0))
+        elif n[0] == "lit":
+            out.append((X_LITERAL, 0, None, float(n[1])))
+        elif n[0] == "fn":
+            for a in n[2]:
+                walk(a)
+            out.append((ARITH_FUNCS[n[1]], len(n[2]), None, 0.0))
+        else:
+            raise ValueError("CAST in an expression is not supported")
+    walk(e)
+    return out
+
+
+def check_expr(e) -> None:
+    """The arities of the reference's transform functions and the library's limits (32 nodes, 8 columns)."""
+    def walk(n):
+        if n[0] != "fn":
+            return 1
+        kind, k = ARITH_FUNCS[n[1]], len(n[2])
+        if kind in (X_ADD, X_MULT, X_LEAST, X_GREATEST):
+            if k < 2:
+                raise ValueError(f"{n[1]} takes two or more arguments")
+        elif kind in (X_SUB, X_DIV, X_MOD):
+            if k != 2:
+                raise ValueError(f"{n[1]} takes exactly two arguments")
+        else:
+            if k != 1:
+                raise ValueError(f"{n[1]} takes exactly one argument")
+            if n[2][0][0] == "lit":
+                raise ValueError(f"{n[1]} of a literal is not supported (the reference requires a non-literal argument)")
+        return 1 + sum(walk(a) for a in n[2])
+    if walk(e) > 32:
+        raise ValueError("an expression takes at most 32 nodes")
+    if len(expr_columns(e)) > 8:
+        raise ValueError("an expression takes at most 8 distinct columns")
+    if not expr_columns(e):
+        raise ValueError("an expression needs a column")
+
+
+def expression(text: str):
+    """The parsed tree of an expression's text (canonical or as written); None for a plain column, a key transform
+    and COUNT's `*`."""
+    return _expression(text) if "(" in text else None
+
+
+@functools.lru_cache(maxsize=512)
+def _expression(text: str):
+    p = _Parser(text)
+    if p.transform_ahead():
+        return None
+    e = p.value_expr()
+    if p.peek()[0] != "eof":
+        raise ValueError(f"unexpected trailing token {p.peek()}")
+    return None if e[0] == "col" else e
+
+
+def parse_expression(text: str):
+    """The tree of an arithmetic expression as written (`a * b + 2`) or in canonical text; a plain column is
+    ('col', name)."""
+    p = _Parser(text)
+    e = p.value_expr()
+    if p.peek()[0] != "eof":
+        raise ValueError(f"unexpected trailing token {p.peek()}")
+    return e
+
+
 @dataclasses.dataclass
 class QueryContext:
     table: str
@@ -364,6 +509,30 @@ class QueryContext:
 
     def has_filtered_aggregations(self) -> bool:
         return any(a.filter is not None for a in self.aggregations)
+
+    def expressions(self) -> List[str]:
+        """The texts of the query's arithmetic expressions (in filters, aggregation arguments and filters, GROUP BY,
+        SELECT and ORDER BY items), each once; not the two-column form SUM / MIN / MAX / AVG keep (Aggregation.expr)."""
+        out: List[str] = []
+
+        def note(text):
+            if text != "*" and text not in out and expression(text) is not None:
+                out.append(text)
+        for clause in self.cnf:
+            for p, _ in clause:
+                note(p.column)
+        for a in self.aggregations:
+            if a.expr is None:
+                note(a.column)
+            for clause in a.cnf:
+                for p, _ in clause:
+                    note(p.column)
+        for g in list(self.group_by) + list(self.select_columns):
+            note(g)
+        if self.is_selection():
+            for c, _ in self.order_by:
+                note(c)
+        return out
 
     def is_selection(self) -> bool:
         """SELECT columns [ORDER BY ...] LIMIT n: neither aggregations nor GROUP BY (SelectionPlanNode)."""
@@ -432,7 +601,7 @@ class QueryContext:
 
 # ---------------------------------------------------------------------------------------- parser
 _TOKEN = re.compile(r"\s*(?:(?P<num>-?\d+\.\d*(?:[eE][-+]?\d+)?|-?\d+(?:[eE][-+]?\d+)?)|(?P<str>'(?:[^']|'')*')"
-                    r"|(?P<op><>|!=|<=|>=|=|<|>|\(|\)|,|\*|\+|-)|(?P<id>[A-Za-z_][A-Za-z0-9_.$]*))")
+                    r"|(?P<op><>|!=|<=|>=|=|<|>|\(|\)|,|\*|\+|-|/|%)|(?P<id>[A-Za-z_][A-Za-z0-9_.$]*))")
 
 
 def _tokenize(sql: str):
@@ -514,7 +683,10 @@ class _Parser:
                 raise ValueError(f"{func}: expected a column or a literal at {tok}")
             self.i += 1
             args.append(tok)
-            if self.peek() != ("op", ","):
+            nxt = self.peek()
+            if nxt[0] == "num" or (nxt[0] == "op" and nxt[1] in ("+", "-", "*", "/", "%", "(")):
+                raise ValueError(f"{func} of an expression is not supported (a key transform takes an INT / LONG column)")
+            if nxt != ("op", ","):
                 break
             self.i += 1
         self.eat_op(")")
@@ -523,7 +695,103 @@ class _Parser:
     def key_item(self) -> str:
         """A GROUP BY / SELECT / ORDER BY item that is not an aggregation: a column, or a key transform as its
         canonical text."""
-        return self.transform_call().text if self.transform_ahead() else self.ident()
+        if self.transform_ahead():
+            return self.transform_call().text
+        e = self.value_expr()
+        if e[0] == "col":
+            return e[1]
+        check_expr(e)
+        return expr_text(e)
+
+    # -- arithmetic expressions: unary minus on literals, * / %, + -, parentheses, the function calls --
+    def value_expr(self):
+        node = self.value_term()
+        while True:
+            tok = self.peek()
+            if tok[0] == "op" and tok[1] in ("+", "-"):
+                self.i += 1
+                node = ("fn", ARITH_OPS[tok[1]], [node, self.value_term()])
+            elif tok[0] == "num" and _is_negative(tok[1]):  # `a -1`: the tokenizer glued the operator to the literal
+                node = ("fn", "minus", [node, self.value_term(strip_minus=True)])
+            else:
+                return node
+
+    def value_term(self, strip_minus=False):
+        node = self.value_unary(strip_minus)
+        while self.peek()[0] == "op" and self.peek()[1] in ("*", "/", "%"):
+            op = self.peek()[1]
+            self.i += 1
+            node = ("fn", ARITH_OPS[op], [node, self.value_unary()])
+        return node
+
+    def value_unary(self, strip_minus=False):
+        tok = self.peek()
+        if tok[0] == "num":
+            self.i += 1
+            return ("lit", -tok[1] if strip_minus else tok[1])
+        if tok[0] == "str":  # a quoted number, as the canonical text prints its literals
+            self.i += 1
+            try:
+                return ("lit", int(tok[1]))
+            except ValueError:
+                try:
+                    return ("lit", float(tok[1]))
+                except ValueError:
+                    raise ValueError(f"string literal {tok[1]!r} in an arithmetic expression") from None
+        if tok == ("op", "-"):
+            if self.peek(1)[0] != "num":
+                raise ValueError("unary minus is supported on literals only")
+            self.i += 2
+            return ("lit", -self.peek(-1)[1])
+        if tok == ("op", "("):
+            self.i += 1
+            e = self.value_expr()
+            self.eat_op(")")
+            return e
+        if tok[0] != "id":
+            raise ValueError(f"expected a column, a literal or a function call at {tok}")
+        if self.kw("CAST") and self.peek(1) == ("op", "("):
+            return ("cast", self.operand())
+        if tok[1].upper() == "CASE":
+            raise ValueError("CASE is not supported in an expression")
+        if self.peek(1) != ("op", "("):
+            return ("col", self.ident())
+        name = tok[1].replace("_", "").lower()
+        if name in KEY_TRANSFORMS:
+            raise ValueError(f"the key transform {tok[1]} inside an expression is not supported (only as a GROUP BY key)")
+        if agg_head(tok[1]):
+            raise ValueError(f"the aggregation {tok[1]} inside an expression is not supported")
+        if name not in ARITH_FUNCS:
+            why = " (its result is not bit-reproducible on the device)" if name in UNSUPPORTED_FUNCS else ""
+            raise ValueError(f"function {tok[1]} is not supported in an expression{why}: only "
+                             "add sub mult div mod abs ceil floor sqrt sign least greatest")
+        self.i += 2
+        args = [self.value_expr()]
+        while self.peek() == ("op", ","):
+            self.i += 1
+            args.append(self.value_expr())
+        self.eat_op(")")
+        return ("fn", name, args)
+
+    def agg_arg(self, func: str):
+        """An aggregation's argument: (column or canonical expression text, two-column (op, a, b) or None). times |
+        minus | plus of two plain columns (CAST(column AS numeric type) counts as the column) keeps the two-column
+        form of pinot_amd_query_add_aggregation_expr under every function, as before: SUM / MIN / MAX / AVG /
+        MINMAXRANGE take it, with the exact int64 sum of INT operands, and the value-set functions keep refusing it
+        ("takes one column"; PERCENTILE(a + b + 0, 95) is an expression). Every other expression is a virtual column
+        named by its text."""
+        e = self.value_expr()
+        if e[0] == "col":
+            return e[1], None
+        if e[0] == "cast":
+            return e[1], None
+        if (e[0] == "fn" and e[1] in ("times", "minus", "plus") and len(e[2]) == 2
+                and all(a[0] in ("col", "cast") for a in e[2])):
+            a, b = e[2][0][1], e[2][1][1]
+            op = {"times": "MUL", "minus": "SUB", "plus": "ADD"}[e[1]]
+            return f"{EXPR_FUNC[op]}({a},{b})", (op, a, b)
+        check_expr(e)
+        return expr_text(e), None
 
     # -- grammar --
     def query(self) -> QueryContext:
@@ -539,13 +807,7 @@ class _Parser:
                     self.i += 1
                     col = "*"
                 else:
-                    col = self.operand()
-                    if self.peek()[0] == "op" and self.peek()[1] in EXPR_OPS:
-                        op = EXPR_OPS[self.peek()[1]]
-                        self.i += 1
-                        col2 = self.operand()
-                        expr = (op, col, col2)
-                        col = f"{EXPR_FUNC[op]}({col},{col2})"
+                    col, expr = self.agg_arg(func)
                 param = self.percentile_arg(func, param)
                 self.eat_op(")")
                 agg_filter = self.agg_filter()
@@ -669,8 +931,11 @@ class _Parser:
         if tok[0] == "id" and agg_head(tok[1]) and self.peek(1) == ("op", "("):
             func, param = agg_head(tok[1])
             self.i += 2
-            col = "*" if self.peek() == ("op", "*") else self.peek()[1]
-            self.i += 1
+            if self.peek() == ("op", "*"):
+                col = "*"
+                self.i += 1
+            else:
+                col, _ = self.agg_arg(func)
             param = self.percentile_arg(func, param)
             self.eat_op(")")
             expr = agg_text(func, col, param)
@@ -707,14 +972,28 @@ class _Parser:
             self.i += 1
             return FilterContext.not_(self.not_expr())
         if self.peek() == ("op", "("):
-            self.i += 1
-            e = self.expr()
-            self.eat_op(")")
-            return e
+            # a parenthesised filter -- or the parenthesis opens an arithmetic expression: `(a - b) * 2 > 5`
+            start = self.i
+            try:
+                self.i += 1
+                e = self.expr()
+                self.eat_op(")")
+                nxt = self.peek()
+                if not ((nxt[0] == "op" and nxt[1] not in (")", ",")) or nxt[0] == "num"
+                        or self.kw("IN") or self.kw("NOT", "IN") or self.kw("BETWEEN") or self.kw("NOT", "BETWEEN")):
+                    return e
+            except ValueError:
+                pass
+            self.i = start
         return self.comparison()
 
     def comparison(self) -> FilterContext:
-        col = self.ident()
+        lhs = self.value_expr()
+        if lhs[0] == "col":
+            col = lhs[1]
+        else:
+            check_expr(lhs)
+            col = expr_text(lhs)
         if self.kw("NOT", "IN") or self.kw("IN"):
             neg = self.kw("NOT")
             self.i += 2 if neg else 1
@@ -752,6 +1031,10 @@ class _Parser:
         if op == ">=":
             return FilterContext.pred(Predicate("RANGE", col, lower=v, lower_inclusive=True))
         raise ValueError(f"unsupported operator {op}")
+
+
+def _is_negative(v) -> bool:
+    return v < 0 or (isinstance(v, float) and v == 0 and math.copysign(1.0, v) < 0)
 
 
 _SET_OPTION = re.compile(r"^\s*SET\s+([A-Za-z_][A-Za-z0-9_]*)\s*=\s*'?([^;']*)'?\s*;", re.IGNORECASE)
@@ -891,7 +1174,7 @@ def split_distinct_count(qc: QueryContext):
         if a.func in VALUE_SET_FUNCS:
             if a.expr is not None or a.column == "*":
                 raise ValueError(f"{a.func} takes one column")
-            if a.column in seen:   # PERCENTILE / DISTINCTSUM / DISTINCTAVG / DISTINCTCOUNT of one column share
+            if a.column in seen:  # PERCENTILE / DISTINCTSUM / DISTINCTAVG / DISTINCTCOUNT of one column share
                 continue           # its query: the sub query of the first of them (fold_distinct_count)
             seen.add(a.column)
             subs.append((i, dataclasses.replace(qc, aggregations=[Aggregation("COUNT", "*")], order_by=[],
