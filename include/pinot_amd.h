@@ -53,7 +53,11 @@ enum pinot_amd_fwd_encoding {
 
 /* Predicate types (pinot-common/.../request/context/predicate/Predicate.java Type) */
 enum pinot_amd_predicate_type { PINOT_AMD_EQ = 0, PINOT_AMD_NOT_EQ = 1, PINOT_AMD_IN = 2, PINOT_AMD_NOT_IN = 3,
-                                PINOT_AMD_RANGE = 4 };
+                                PINOT_AMD_RANGE = 4,
+                                /* RegexpLikePredicate on a STRING column: the pattern is h_values_s[0], num_values 1;
+                                 * _CI is match parameter 'i' (CASE_INSENSITIVE | UNICODE_CASE). A LIKE is the
+                                 * REGEXP_LIKE_CI of pinot_amd_like_to_regexp's pattern. */
+                                PINOT_AMD_REGEXP_LIKE = 5, PINOT_AMD_REGEXP_LIKE_CI = 6 };
 
 /* Aggregation functions (pinot-segment-spi/.../AggregationFunctionType.java) */
 enum pinot_amd_agg_type { PINOT_AMD_AGG_COUNT = 0, PINOT_AMD_AGG_SUM = 1, PINOT_AMD_AGG_MIN = 2,
@@ -235,6 +239,24 @@ int pinot_amd_bitset_to_doc_ids(const uint64_t* d_bitset, int64_t num_docs, int3
                                 void* stream);
 int pinot_amd_bitset_count(const uint64_t* d_bitset, int64_t num_docs, int64_t* h_count, void* stream);
 
+/* RegexpLikePredicateEvaluatorFactory.DictIdBasedRegexpLikePredicateEvaluator
+ * (core/operator/filter/predicate/RegexpLikePredicateEvaluatorFactory.java): the dictIds of a STRING column whose
+ * values the pattern matches, as java.util.regex's Matcher.find() over the value would (flags 0, or
+ * CASE_INSENSITIVE | UNICODE_CASE when case_insensitive is set). h_mask_words receives bit d of 32-bit word d / 32
+ * for dictId d (mask_words >= ceil(cardinality / 32); the words behind the dictionary are zeroed), num_matching
+ * the count; either may be NULL. The pattern is compiled to a DFA that the device walks one lane per dictionary value
+ * or the host walks value by value: PINOT_AMD_REGEX_DEVICE=always|never|auto (auto: the device at 16384 values and
+ * above, the measured break-even). A pattern outside the supported subset fails with PINOT_AMD_EUNSUPPORTED and the construct's name, one that
+ * java.util.regex rejects too with PINOT_AMD_EINVAL, a column that is not STRING with PINOT_AMD_EINVAL. */
+int pinot_amd_segment_regexp_match_dictionary(pinot_amd_segment* seg, const char* column, const char* pattern,
+                                              int32_t case_insensitive, uint32_t* h_mask_words, int64_t mask_words,
+                                              int64_t* num_matching);
+/* Compiles the pattern and drops the automaton: 0, or the error pinot_amd_query_add_predicate would return. */
+int pinot_amd_regexp_check(const char* pattern, int32_t case_insensitive);
+/* RegexpPatternConverterUtils.likeToRegexpLike: the REGEXP_LIKE pattern of a LIKE pattern, written NUL-terminated to
+ * h_out. Returns the pattern's length (without the NUL); when that is >= capacity nothing is written. */
+int64_t pinot_amd_like_to_regexp(const char* like, char* h_out, int64_t capacity);
+
 /* ------------------------------------------------------------------------------------------------
  * Query plan: FilterPlanNode + AggregationPlanNode / GroupByPlanNode + CombinePlanNode.
  * A query is compiled once on the host (predicate evaluation per segment mirrors
@@ -247,10 +269,10 @@ typedef struct pinot_amd_query pinot_amd_query;
 typedef struct pinot_amd_predicate_spec {
   const char* column;
   int32_t type;               /* pinot_amd_predicate_type */
-  int32_t num_values;         /* EQ/NOT_EQ: 1; IN/NOT_IN: n; RANGE: unused */
+  int32_t num_values;         /* EQ/NOT_EQ/REGEXP_LIKE[_CI]: 1; IN/NOT_IN: n; RANGE: unused */
   const int64_t* h_values_i;  /* values for INT/LONG columns */
   const double* h_values_d;   /* values for FLOAT/DOUBLE columns */
-  const char* const* h_values_s; /* values for STRING columns */
+  const char* const* h_values_s; /* values for STRING columns; REGEXP_LIKE[_CI]: the pattern (UTF-8) */
   /* RANGE (RangePredicate): bounds in the column's value domain */
   int32_t lower_unbounded, upper_unbounded, lower_inclusive, upper_inclusive;
   int64_t lower_i, upper_i;

@@ -88,6 +88,10 @@ SIGNATURES = {
     "pinot_amd_bitset_not": (C.c_int, [_P, _P, C.c_int64, _P]),
     "pinot_amd_bitset_to_doc_ids": (C.c_int, [_P, C.c_int64, _P, _I64P, _P]),
     "pinot_amd_bitset_count": (C.c_int, [_P, C.c_int64, _I64P, _P]),
+    "pinot_amd_segment_regexp_match_dictionary": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.c_int32,
+                                                            C.POINTER(C.c_uint32), C.c_int64, _I64P]),
+    "pinot_amd_regexp_check": (C.c_int, [C.c_char_p, C.c_int32]),
+    "pinot_amd_like_to_regexp": (C.c_int64, [C.c_char_p, C.c_char_p, C.c_int64]),
     "pinot_amd_query_create": (C.c_int, [_PP]),
     "pinot_amd_query_destroy": (C.c_int, [_P]),
     "pinot_amd_query_add_predicate": (C.c_int, [_P, C.c_int32, C.POINTER(PredicateSpec), C.c_int32]),

@@ -32,6 +32,7 @@
 #include "expr.h"
 #include "jit.h"
 #include "kernels.h"
+#include "regex_dfa.h"
 
 using namespace pamd;
 
@@ -87,6 +88,7 @@ static const std::set<std::string>& kept_knobs() {
       "PINOT_AMD_PARTITIONED",
       "PINOT_AMD_PART_CAP_SCALE",
       "PINOT_AMD_PREFETCH",
+      "PINOT_AMD_REGEX_DEVICE",
       "PINOT_AMD_SAMPLE_STRIDE",
       "PINOT_AMD_SCAN_GROUP",
       "PINOT_AMD_SELECT",
@@ -375,6 +377,12 @@ struct Column {
   int32_t mv_max = 0;
   int64_t mv_bm_off = 0, mv_raw_off = 0;  // byte offsets of the bitmap and of the dictId stream in the file
   DevBuf mv_tfd;
+  // device copy of a STRING dictionary for the pattern predicates, built at the first one (string_dict_device) and
+  // kept with the column: the values' UTF-8 bytes concatenated in dictId order (padded like every staged buffer, so a
+  // dword load at a value's last byte stays inside) and card + 1 int32 byte offsets. sdict_state 0: not built, 1:
+  // built, 2: the bytes do not fit int32 offsets (the host runner answers). Guarded by g_sdict_mu.
+  mutable DevBuf sdict_bytes, sdict_offs;
+  mutable int sdict_state = 0;
 };
 
 // the device view of a staged MV column
@@ -1344,6 +1352,191 @@ int pinot_amd_bitset_to_doc_ids(const uint64_t* d_bitset, int64_t num_docs, int3
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------
+// REGEXP_LIKE / LIKE: pattern -> DFA (regex_dfa.h) -> the matching dictIds of a STRING dictionary
+// ------------------------------------------------------------------------------------------------
+static bool is_regex_type(int t) { return t == PINOT_AMD_REGEXP_LIKE || t == PINOT_AMD_REGEXP_LIKE_CI; }
+
+// Compiled patterns are kept (a caller re-creates its query for every execution); a refused pattern is not, and fails
+// with the construct's name.
+static int regex_compiled(const std::string& pattern, bool ci, std::shared_ptr<const pamd_regex::Dfa>* out) {
+  static std::mutex mu;
+  static std::map<std::pair<std::string, bool>, std::shared_ptr<const pamd_regex::Dfa>> cache;
+  const std::pair<std::string, bool> key(pattern, ci);
+  {
+    std::lock_guard<std::mutex> g(mu);
+    auto it = cache.find(key);
+    if (it != cache.end()) {
+      *out = it->second;
+      return 0;
+    }
+  }
+  auto dfa = std::make_shared<pamd_regex::Dfa>();
+  std::string err;
+  if (const int rc = pamd_regex::compile(pattern, ci, dfa.get(), &err))
+    return fail(rc == pamd_regex::kInvalid ? PINOT_AMD_EINVAL : PINOT_AMD_EUNSUPPORTED, "regexp_like '%s'%s: %s",
+                pattern.c_str(), ci ? " 'i'" : "", err.c_str());
+  std::lock_guard<std::mutex> g(mu);
+  if (cache.size() >= 256) cache.clear();
+  cache[key] = dfa;
+  *out = std::move(dfa);
+  return 0;
+}
+
+// PINOT_AMD_REGEX_DEVICE=always|never|auto: which runner walks the table over a dictionary. auto: the device at
+// kRegexDeviceMinCard values and above, the measured break-even of the two runners rounded up to a power of two
+// (profiles/regex_probe.py, DESIGN.md §7: at 1000 values the host runner is as fast or faster for every pattern, at
+// 10000 the device call is for every pattern; the device call costs ~0.06 ms whatever the dictionary up to 10^5 values).
+constexpr int32_t kRegexDeviceMinCard = 16384;
+enum { REGEX_AUTO = 0, REGEX_ALWAYS = 1, REGEX_NEVER = 2 };
+static int regex_policy() {
+  if (const char* pol = knob("PINOT_AMD_REGEX_DEVICE")) {
+    if (strcmp(pol, "always") == 0) return REGEX_ALWAYS;
+    if (strcmp(pol, "never") == 0) return REGEX_NEVER;
+  }
+  return REGEX_AUTO;
+}
+
+static std::mutex g_sdict_mu;  // guards every column's sdict_* fields
+// the device copy of a STRING dictionary, built on first use; false when the column has none (sdict_state 2)
+static int string_dict_device(pinot_amd_segment* seg, const Column& c, bool* have) {
+  std::lock_guard<std::mutex> g(g_sdict_mu);
+  if (c.sdict_state == 0) {
+    size_t total = 0;
+    for (const std::string& v : c.dict_s) total += v.size();
+    if (total + kPadBytes > (size_t)std::numeric_limits<int32_t>::max()) {
+      c.sdict_state = 2;
+    } else {
+      std::vector<uint8_t> bytes;
+      bytes.reserve(total);
+      std::vector<int32_t> offs;
+      offs.reserve(c.dict_s.size() + 1);
+      for (const std::string& v : c.dict_s) {
+        offs.push_back((int32_t)bytes.size());
+        bytes.insert(bytes.end(), v.begin(), v.end());
+      }
+      offs.push_back((int32_t)bytes.size());
+      if (int rc = c.sdict_bytes.alloc_copy(bytes.data(), bytes.size(), kPadBytes)) return rc;
+      if (int rc = c.sdict_offs.alloc_copy(offs.data(), offs.size() * 4, 64)) {
+        c.sdict_bytes.reset();
+        return rc;
+      }
+      seg->device_bytes += (int64_t)(c.sdict_bytes.n + c.sdict_offs.n);
+      c.sdict_state = 1;
+    }
+  }
+  *have = c.sdict_state == 1;
+  return 0;
+}
+
+// The dictIds of `column` that the automaton matches, per segment of `segs`: masks[k] holds bit d of 64-bit word
+// d / 64 for dictId d of segs[k]. The dictionaries the knob sends to the device are matched by ONE launch through a
+// descriptor array, followed by one copy of all their masks and one synchronisation, however many segments there are;
+// the others by the host runner over the same table.
+static int regex_resolve(const std::vector<pinot_amd_segment*>& segs, const std::string& column,
+                         const pamd_regex::Dfa& dfa, hipStream_t st, std::vector<std::vector<uint64_t>>* masks) {
+  const int pol = regex_policy();
+  masks->assign(segs.size(), std::vector<uint64_t>());
+  std::vector<DevRegexDict> descs;
+  std::vector<size_t> desc_seg;
+  int64_t waves = 0;
+  for (size_t k = 0; k < segs.size(); ++k) {
+    const Column& c = *segs[k]->cols.at(column);
+    const size_t card = c.dict_s.size();
+    std::vector<uint64_t>& m = (*masks)[k];
+    m.assign((card + 63) / 64, 0ull);
+    bool dev = card > 0 && (pol == REGEX_ALWAYS || (pol == REGEX_AUTO && card >= (size_t)kRegexDeviceMinCard));
+    if (dev)
+      if (int rc = string_dict_device(segs[k], c, &dev)) return rc;
+    if (!dev) {
+      for (size_t d = 0; d < card; ++d)
+        if (pamd_regex::match(dfa, c.dict_s[d].data(), c.dict_s[d].size())) m[d >> 6] |= 1ull << (d & 63);
+      continue;
+    }
+    DevRegexDict d{};
+    d.bytes = (const uint32_t*)c.sdict_bytes.p;
+    d.offs = (const int32_t*)c.sdict_offs.p;
+    d.first_wave = d.out_word0 = waves;
+    d.card = (int32_t)card;
+    descs.push_back(d);
+    desc_seg.push_back(k);
+    waves += (int64_t)m.size();
+  }
+  if (descs.empty()) return 0;
+  std::vector<uint32_t> words(64 + (dfa.table.size() + 1) / 2, 0u);
+  memcpy(words.data(), dfa.class_of, 256);
+  memcpy(words.data() + 64, dfa.table.data(), dfa.table.size() * sizeof(uint16_t));
+  DevBuf d_dfa, d_descs, d_masks;
+  if (int rc = d_dfa.alloc_copy(words.data(), words.size() * 4, 0)) return rc;
+  if (int rc = d_descs.alloc_copy(descs.data(), descs.size() * sizeof(DevRegexDict), 0)) return rc;
+  if (int rc = d_masks.alloc((size_t)waves * 8)) return rc;
+  HIP_OK(launch_dict_regex_match((const DevRegexDict*)d_descs.p, (int32_t)descs.size(), waves, (const uint32_t*)d_dfa.p,
+                                 (int32_t)words.size(), dfa.num_classes, dfa.start, (unsigned long long*)d_masks.p, st));
+  std::vector<uint64_t> h((size_t)waves);
+  HIP_OK(hipMemcpyAsync(h.data(), d_masks.p, (size_t)waves * 8, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  for (size_t j = 0; j < descs.size(); ++j) {
+    std::vector<uint64_t>& m = (*masks)[desc_seg[j]];
+    std::copy(h.begin() + descs[j].out_word0, h.begin() + descs[j].out_word0 + (int64_t)m.size(), m.begin());
+  }
+  return 0;
+}
+
+static std::vector<int32_t> ids_of_mask(const std::vector<uint64_t>& m, int64_t card) {
+  std::vector<int32_t> ids;
+  for (size_t w = 0; w < m.size(); ++w)
+    for (uint64_t b = m[w]; b; b &= b - 1) {
+      const int64_t d = (int64_t)w * 64 + __builtin_ctzll(b);
+      if (d < card) ids.push_back((int32_t)d);
+    }
+  return ids;
+}
+
+extern "C" {
+
+int pinot_amd_regexp_check(const char* pattern, int32_t case_insensitive) {
+  if (!pattern) return fail(PINOT_AMD_EINVAL, "regexp_check: null pattern");
+  std::shared_ptr<const pamd_regex::Dfa> dfa;
+  return regex_compiled(pattern, case_insensitive != 0, &dfa);
+}
+
+int64_t pinot_amd_like_to_regexp(const char* like, char* h_out, int64_t capacity) {
+  if (!like) return fail(PINOT_AMD_EINVAL, "like_to_regexp: null pattern");
+  const std::string r = pamd_regex::like_to_regexp(like);
+  if (h_out && (int64_t)r.size() < capacity) memcpy(h_out, r.c_str(), r.size() + 1);
+  return (int64_t)r.size();
+}
+
+int pinot_amd_segment_regexp_match_dictionary(pinot_amd_segment* seg, const char* column, const char* pattern,
+                                              int32_t case_insensitive, uint32_t* h_mask_words, int64_t mask_words,
+                                              int64_t* num_matching) {
+  const char* what = "regexp_match_dictionary";
+  if (!seg || !column || !pattern) return fail(PINOT_AMD_EINVAL, "%s: bad arguments", what);
+  auto it = seg->cols.find(column);
+  if (it == seg->cols.end()) return fail(PINOT_AMD_EINVAL, "%s: no column %s", what, column);
+  const Column& c = *it->second;
+  // RegexpLikePredicateEvaluatorFactory: checkArgument(dataType.getStoredType() == DataType.STRING)
+  if (c.type != T_STRING) return fail(PINOT_AMD_EINVAL, "%s: column %s is not STRING", what, column);
+  const int64_t card = (int64_t)c.dict_s.size();
+  if (h_mask_words && mask_words < (card + 31) / 32)
+    return fail(PINOT_AMD_EINVAL, "%s: %lld mask words for %lld values", what, (long long)mask_words, (long long)card);
+  std::shared_ptr<const pamd_regex::Dfa> dfa;
+  if (int rc = regex_compiled(pattern, case_insensitive != 0, &dfa)) return rc;
+  std::vector<std::vector<uint64_t>> masks;
+  if (int rc = regex_resolve({seg}, column, *dfa, nullptr, &masks)) return rc;
+  int64_t n = 0;
+  for (uint64_t w : masks[0]) n += __builtin_popcountll(w);
+  if (num_matching) *num_matching = n;
+  if (h_mask_words) {
+    memset(h_mask_words, 0, (size_t)mask_words * 4);
+    for (int64_t w = 0; w < (card + 31) / 32; ++w)
+      h_mask_words[w] = (uint32_t)(masks[0][(size_t)(w >> 1)] >> ((w & 1) * 32));
+  }
+  return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
 // Query
 // ------------------------------------------------------------------------------------------------
 struct PredSpec {
@@ -1493,7 +1686,15 @@ static int make_pred_spec(const char* what, pinot_amd_query* q, int32_t clause, 
   s.clause = clause;
   s.negate = negate ? 1 : 0;
   s.use_inv = p->use_inverted_index;
-  if (p->type < PINOT_AMD_EQ || p->type > PINOT_AMD_RANGE) return fail(PINOT_AMD_EINVAL, "%s: bad type", what);
+  if (p->type < PINOT_AMD_EQ || p->type > PINOT_AMD_REGEXP_LIKE_CI) return fail(PINOT_AMD_EINVAL, "%s: bad type", what);
+  if (is_regex_type(p->type)) {
+    // RegexpLikePredicate: the pattern compiles here, so a refused one fails the call that names it
+    if (p->num_values != 1 || !p->h_values_s || !p->h_values_s[0])
+      return fail(PINOT_AMD_EINVAL, "%s: REGEXP_LIKE takes one pattern in h_values_s[0]", what);
+    s.vs.push_back(p->h_values_s[0]);
+    std::shared_ptr<const pamd_regex::Dfa> dfa;
+    return regex_compiled(s.vs[0], p->type == PINOT_AMD_REGEXP_LIKE_CI, &dfa);
+  }
   if (p->type != PINOT_AMD_RANGE) {
     if (p->num_values < 1) return fail(PINOT_AMD_EINVAL, "%s: no values", what);
     if ((p->type == PINOT_AMD_EQ || p->type == PINOT_AMD_NOT_EQ) && p->num_values != 1)
@@ -2369,9 +2570,11 @@ static bool use_inverted_for(const Column& c, int64_t num_docs, const std::vecto
 // docId-bitset slack behind an inverted-index leaf's words (make_leaf_for_segment): 64 tiles
 constexpr size_t kBitsetSlackBytes = 64 * kTileDocs / 8;
 
-static int make_leaf_uncached(pinot_amd_result* r, int si, const pinot_amd_segment* seg, const PredSpec& p,
+// rx_mask: a pattern predicate's matching dictIds in this segment when the caller resolved them with the batch's other
+// segments (PlanBuild::leaves), else null: resolved here
+static int make_leaf_uncached(pinot_amd_result* r, int si, pinot_amd_segment* seg, const PredSpec& p,
                               const Column& c, int slot, DevLeaf* L, bool* needs_slot, hipStream_t st,
-                              bool decoded_anyway) {
+                              bool decoded_anyway, const std::vector<uint64_t>* rx_mask) {
   memset(L, 0, sizeof(*L));
   L->slot = slot;
   L->clause = p.clause;
@@ -2379,6 +2582,9 @@ static int make_leaf_uncached(pinot_amd_result* r, int si, const pinot_amd_segme
   *needs_slot = true;
   const bool negated_type = p.type == PINOT_AMD_NOT_EQ || p.type == PINOT_AMD_NOT_IN;
   if (negated_type) L->negate ^= 1;
+  // RegexpLikePredicateEvaluatorFactory: checkArgument(dataType.getStoredType() == DataType.STRING)
+  if (is_regex_type(p.type) && c.type != T_STRING)
+    return fail(PINOT_AMD_EINVAL, "regexp_like on column %s, which is not STRING", c.name.c_str());
 
   if (c.enc == ENC_RAW) {
     // raw-value based evaluators
@@ -2455,7 +2661,19 @@ static int make_leaf_uncached(pinot_amd_result* r, int si, const pinot_amd_segme
     if (end < start) end = start;
     is_range = true;
   } else {
-    ids = dict_ids_of_values(p, c);
+    if (is_regex_type(p.type)) {
+      // DictIdBasedRegexpLikePredicateEvaluator: the dictIds whose values the pattern finds a match in
+      std::vector<std::vector<uint64_t>> own;
+      if (!rx_mask) {
+        std::shared_ptr<const pamd_regex::Dfa> dfa;
+        if (int rc = regex_compiled(p.vs.at(0), p.type == PINOT_AMD_REGEXP_LIKE_CI, &dfa)) return rc;
+        if (int rc = regex_resolve({seg}, p.column, *dfa, st, &own)) return rc;
+        rx_mask = &own[0];
+      }
+      ids = ids_of_mask(*rx_mask, c.card);
+    } else {
+      ids = dict_ids_of_values(p, c);
+    }
     if (!ids.empty() && ids.back() - ids.front() + 1 == (int32_t)ids.size()) {
       is_range = true;
       start = ids.front();
@@ -2612,14 +2830,17 @@ constexpr size_t kLeafCacheMax = 256;  // entries per segment (cleared when full
 // predicate, the slot, whether its column is decoded anyway, and the knobs of the inverted-index policy.
 static std::string leaf_cache_key(const PredSpec& p, int slot, bool decoded_anyway) {
   const char* pol = knob("PINOT_AMD_INV_POLICY");
-  return preds_signature({p}) + "|" + std::to_string(slot) + "|" + (decoded_anyway ? "1" : "0") + "|" +
-         std::to_string(expand_group()) + "|" + (pol ? pol : "");
+  std::string key = preds_signature({p}) + "|" + std::to_string(slot) + "|" + (decoded_anyway ? "1" : "0") + "|" +
+                    std::to_string(expand_group()) + "|" + (pol ? pol : "");
+  if (is_regex_type(p.type)) key += "|rx" + std::to_string(regex_policy());
+  return key;
 }
 
 // key: leaf_cache_key(p, slot, decoded_anyway), built by the caller once for every segment
 static int make_leaf_for_segment(pinot_amd_result* r, int si, pinot_amd_segment* seg, const PredSpec& p,
                                  const Column& c, int slot, DevLeaf* L, bool* needs_slot, hipStream_t st,
-                                 bool decoded_anyway, const std::string& key) {
+                                 bool decoded_anyway, const std::string& key,
+                                 const std::vector<uint64_t>* rx_mask = nullptr) {
   std::shared_ptr<const LeafCacheEntry> hit;
   {
     std::lock_guard<std::mutex> g(g_leaf_mu);
@@ -2648,7 +2869,7 @@ static int make_leaf_for_segment(pinot_amd_result* r, int si, pinot_amd_segment*
     return 0;
   }
   const size_t o0 = r->owned.size(), i0 = r->inv_leaves.size(), m0 = r->mv_leaves.size();
-  if (int rc = make_leaf_uncached(r, si, seg, p, c, slot, L, needs_slot, st, decoded_anyway)) return rc;
+  if (int rc = make_leaf_uncached(r, si, seg, p, c, slot, L, needs_slot, st, decoded_anyway, rx_mask)) return rc;
   auto e = std::make_shared<LeafCacheEntry>();
   e->L = *L;
   e->needs_slot = *needs_slot;
@@ -4344,14 +4565,38 @@ int PlanBuild::leaves() {
     pred_decoded[pi] = d ? 1 : 0;
     pred_key[pi] = leaf_cache_key(p, -1, d);
   }
+  // Pattern predicates: the segments that have no cached leaf are resolved together, one launch, one copy and one
+  // synchronisation per predicate (regex_resolve), before the per-segment loop hands each its dictId mask
+  std::map<std::pair<int, size_t>, std::vector<uint64_t>> rx_masks;
+  for (size_t pi = 0; pi < np; ++pi) {
+    const PredSpec& p = all_preds[pi];
+    if (!is_regex_type(p.type)) continue;
+    std::vector<pinot_amd_segment*> todo;
+    std::vector<int> todo_idx;
+    for (int si = 0; si < n; ++si) {
+      if (segs[si]->cols.at(p.column)->type != T_STRING)
+        return fail(PINOT_AMD_EINVAL, "regexp_like on column %s, which is not STRING", p.column.c_str());
+      std::lock_guard<std::mutex> g(g_leaf_mu);
+      if (segs[si]->leaf_cache.count(pred_key[pi])) continue;
+      todo.push_back(segs[si]);
+      todo_idx.push_back(si);
+    }
+    if (todo.empty()) continue;
+    std::shared_ptr<const pamd_regex::Dfa> dfa;
+    if (int rc = regex_compiled(p.vs.at(0), p.type == PINOT_AMD_REGEXP_LIKE_CI, &dfa)) return rc;
+    std::vector<std::vector<uint64_t>> masks;
+    if (int rc = regex_resolve(todo, p.column, *dfa, r->stream, &masks)) return rc;
+    for (size_t k = 0; k < todo.size(); ++k) rx_masks[{todo_idx[k], pi}] = std::move(masks[k]);
+  }
   for (int si = 0; si < n; ++si) {
     for (size_t pi = 0; pi < np; ++pi) {
       const PredSpec& p = all_preds[pi];
       const Column& c = *segs[si]->cols.at(p.column);
       bool needs_slot = false;
       const bool decoded_anyway = pred_decoded[pi] != 0;
+      auto rx = rx_masks.find({si, pi});
       int rc = make_leaf_for_segment(r, si, segs[si], p, c, -1, &seg_leaves[si][pi], &needs_slot, r->stream,
-                                     decoded_anyway, pred_key[pi]);
+                                     decoded_anyway, pred_key[pi], rx == rx_masks.end() ? nullptr : &rx->second);
       if (rc) return rc;
       if (needs_slot) leaf_slot_col[si][pi] = slot_of(p.column);
     }

@@ -95,6 +95,19 @@ hipError_t launch_selection_cut(const uint64_t* sorted, int W, int64_t n, int64_
                                 int64_t total, uint32_t* out_seg, uint32_t* out_doc, hipStream_t st);
 hipError_t launch_selection_gather(const SelCol* cols, int32_t ncols, const uint32_t* row_seg, const uint32_t* row_doc,
                                    int64_t nrows, int64_t* out, hipStream_t st);
+// dict_regex_match_kernel: one STRING dictionary of a batch. bytes: the values' UTF-8 bytes concatenated in dictId
+// order (dword-aligned, pinot_amd_required_padding() bytes of slack behind them); offs: card + 1 byte offsets
+struct DevRegexDict {
+  const uint32_t* bytes;
+  const int32_t* offs;
+  int64_t first_wave;  // waves (64 values each) of the descriptors before this one
+  int64_t out_word0;   // this dictionary's first 64-bit word in the mask buffer (one word per wave)
+  int32_t card, pad;
+};
+// dfa_words: the 256-byte class map, then the table's uint16 row offsets (regex_dfa.h), padded to a dword
+hipError_t launch_dict_regex_match(const DevRegexDict* d_descs, int32_t ndesc, int64_t total_waves,
+                                   const uint32_t* d_dfa_words, int32_t dfa_nwords, int32_t num_classes, uint32_t start,
+                                   unsigned long long* d_masks, hipStream_t st);
 
 // derive.hip
 // A GROUP BY key transform as the transform kernel takes it (by value): pinot_amd_key_transform_spec after

@@ -2736,4 +2736,77 @@ hipError_t launch_selection_gather(const SelCol* cols, int32_t ncols, const uint
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// REGEXP_LIKE / LIKE over STRING dictionaries
+// ------------------------------------------------------------------------------------------------
+// One lane per dictionary value walks the pattern's DFA (regex_dfa.h: a 256-byte class map, then rows of uint16 row
+// offsets; row 0 dead, row nc accepting, class nc - 1 the end of input) over the value's bytes. The automaton is
+// copied into LDS once per block; a lane loads its bytes as dwords of the concatenated buffer (adjacent lanes read
+// adjacent values, so a wave touches one contiguous run of lines) and leaves at the accepting or the dead row. The
+// wave ballots the outcomes and lane 0 stores them as the wave's own two words of the dictId bitmap: no atomics, and
+// the bits behind a dictionary's last value are zero. One launch covers every dictionary of a batch: wave w belongs to
+// the last descriptor whose first_wave is <= w.
+typedef const __attribute__((address_space(1))) uint32_t* RegexBytes;
+typedef const __attribute__((address_space(1))) int32_t* RegexOffs;
+
+__global__ void __launch_bounds__(1024) dict_regex_match_kernel(const DevRegexDict* __restrict__ descs, int32_t ndesc,
+                                                                 int64_t total_waves,
+                                                                 const uint32_t* __restrict__ dfa_words,
+                                                                 int32_t dfa_nwords, uint32_t nc, uint32_t start,
+                                                                 unsigned long long* __restrict__ masks) {
+  extern __shared__ uint32_t regex_lds[];
+  for (int32_t i = (int32_t)threadIdx.x; i < dfa_nwords; i += (int32_t)blockDim.x) regex_lds[i] = dfa_words[i];
+  __syncthreads();
+  const uint8_t* cls = reinterpret_cast<const uint8_t*>(regex_lds);
+  const uint16_t* tab = reinterpret_cast<const uint16_t*>(regex_lds + 64);
+  const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (wave >= total_waves) return;
+  int32_t lo = 0, hi = ndesc - 1;
+  while (lo < hi) {
+    const int32_t mid = (lo + hi + 1) >> 1;
+    if (descs[mid].first_wave <= wave) lo = mid; else hi = mid - 1;
+  }
+  const DevRegexDict d = descs[lo];
+  const int64_t id = (wave - d.first_wave) * 64 + (int64_t)(threadIdx.x & 63);
+  uint32_t row = 0;
+  if (id < (int64_t)d.card) {
+    RegexOffs offs = (RegexOffs)d.offs;
+    RegexBytes words = (RegexBytes)d.bytes;
+    uint32_t pos = (uint32_t)offs[id];
+    const uint32_t end = (uint32_t)offs[id + 1];
+    row = start;
+    while (pos < end && row > nc) {
+      uint32_t v = words[pos >> 2] >> ((pos & 3u) * 8u);  // (reads up to 3 bytes past `end`: the buffer is padded)
+      uint32_t nb = min(4u - (pos & 3u), end - pos);
+      pos += nb;
+      do {
+        row = tab[row + cls[v & 0xffu]];
+        v >>= 8;
+      } while (--nb != 0u && row > nc);
+    }
+    if (row > nc) row = tab[row + nc - 1u];
+  }
+  const unsigned long long m = __ballot(row == nc);
+  if ((threadIdx.x & 63) == 0) masks[d.out_word0 + (wave - d.first_wave)] = m;
+}
+
+hipError_t launch_dict_regex_match(const DevRegexDict* d_descs, int32_t ndesc, int64_t total_waves,
+                                   const uint32_t* d_dfa_words, int32_t dfa_nwords, int32_t num_classes, uint32_t start,
+                                   unsigned long long* d_masks, hipStream_t st) {
+  if (ndesc <= 0 || total_waves <= 0) return hipSuccess;
+  const size_t lds = (size_t)dfa_nwords * 4;
+  if (lds > 64 * 1024 || num_classes < 2) return hipErrorInvalidValue;
+  // occupancy: the walk is a chain of dependent LDS lookups, hidden by resident waves only. 160 KiB of LDS per CU:
+  // 256-thread blocks keep 32 waves resident up to 20 KiB each, 1024-thread blocks (two per CU) up to 64 KiB
+  const int block = lds > 20 * 1024 ? 1024 : 256;
+  const int64_t wpb = block / 64;
+  const int64_t grid = (total_waves + wpb - 1) / wpb;
+  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+  if (lds > 48 * 1024)
+    (void)hipFuncSetAttribute((const void*)dict_regex_match_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(dict_regex_match_kernel, dim3((unsigned)grid), dim3(block), lds, st, d_descs, ndesc, total_waves,
+                     d_dfa_words, dfa_nwords, (uint32_t)num_classes, start, d_masks);
+  return hipGetLastError();
+}
+
 }  // namespace pamd

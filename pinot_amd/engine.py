@@ -35,7 +35,7 @@ from .segment import ColumnBuffers, SegmentBuffers, DOUBLE, FLOAT, INT, LONG, ST
 
 TYPE_CODE = {INT: 0, LONG: 1, FLOAT: 2, DOUBLE: 3, STRING: 4}
 ENC_CODE = {"FIXED_BIT": 0, "RAW": 1, "SORTED": 2, "FIXED_BIT_MV": 3}
-PRED_CODE = {"EQ": 0, "NOT_EQ": 1, "IN": 2, "NOT_IN": 3, "RANGE": 4}
+PRED_CODE = {"EQ": 0, "NOT_EQ": 1, "IN": 2, "NOT_IN": 3, "RANGE": 4, "REGEXP_LIKE": 5}  # (6: REGEXP_LIKE, 'i')
 AGG_CODE = {"COUNT": 0, "SUM": 1, "MIN": 2, "MAX": 3, "SUMLONG": 4, "AVG": 5, "MINMAXRANGE": 6,
             "DISTINCTCOUNT": 7, "PERCENTILE": 8, "DISTINCTSUM": 9, "DISTINCTAVG": 10,
             "COUNTMV": 11, "SUMMV": 12, "MINMV": 13, "MAXMV": 14, "AVGMV": 15, "MINMAXRANGEMV": 16}
@@ -123,6 +123,19 @@ class ImmutableSegment:
             return None
         return {"lo_bits": lo.value, "hi_bits": hi.value, "base": base.value, "bytes": nbytes.value}
 
+    def regexp_match_dictionary(self, column: str, pattern: str, case_insensitive: bool = False) -> np.ndarray:
+        """DictIdBasedRegexpLikePredicateEvaluator: a bool per dictId of a STRING column, True where the pattern finds
+        a match in the value (the runner PINOT_AMD_REGEX_DEVICE selects)."""
+        card = self.columns[column].cardinality
+        words = np.zeros((card + 31) // 32 + 1, dtype=np.uint32)
+        n = C.c_int64()
+        check(lib().pinot_amd_segment_regexp_match_dictionary(
+            self._h, column.encode(), pattern.encode(), 1 if case_insensitive else 0,
+            words.ctypes.data_as(C.POINTER(C.c_uint32)), len(words), C.byref(n)), f"regexp_match_dictionary({column})")
+        bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:card].astype(bool)
+        assert int(bits.sum()) == n.value
+        return bits
+
     def column_fwd_ptr(self, column: str) -> int:
         p = lib().pinot_amd_segment_column_fwd(self._h, column.encode())
         if not p:
@@ -206,6 +219,21 @@ def _predicate_spec(pred, column, use_inverted: bool, keep: list, abi_name: Opti
     keep.append(s.column)
     s.type = PRED_CODE[pred.type]
     st = column.stored_type
+    if pred.type == "REGEXP_LIKE":
+        # the pattern is h_values_s[0]; a refused pattern or a column that is not STRING is the caller's error
+        if pred.case_insensitive:
+            s.type += 1
+        if st != STRING:
+            raise ValueError(f"regexp_like on column {pred.column}, which is {st}, not STRING")
+        pat = pred.values[0].encode()
+        if lib().pinot_amd_regexp_check(pat, 1 if pred.case_insensitive else 0) != 0:
+            raise ValueError(lib().pinot_amd_last_error().decode(errors="replace"))
+        s.use_inverted_index = 1 if (use_inverted and column.inverted is not None) else 0
+        s.num_values = 1
+        arr = (C.c_char_p * 1)(pat)
+        keep.append(arr)
+        s.h_values_s = arr
+        return s
     s.use_inverted_index = 1 if (use_inverted and column.inverted is not None and pred.type != "RANGE") else 0
     if pred.type == "RANGE":
         s.lower_unbounded = 1 if pred.lower is None else 0
@@ -696,7 +724,7 @@ class ServerQueryExecutor:
         """FilterPlanNode -> BlockDocIdSet: ascending matching docIds of each segment (the filter
         runs on the device into a dense bitset, compacted with ballot / prefix sums)."""
         import torch
-        qc = parse_sql(query) if isinstance(query, str) else query
+        qc = parse_sql(query, pattern_predicates=True) if isinstance(query, str) else query
         L = lib()
         qh, _ = self._compile(qc, segments)
         try:
@@ -745,7 +773,7 @@ class ServerQueryExecutor:
         """Run a query over HBM-resident segments. key_space (optional): group-by column -> the values of
         its global key space (dist.global_key_space: the union of every rank's dictionaries), so that
         every rank's dense group table indexes the same groups."""
-        qc = parse_sql(query) if isinstance(query, str) else query
+        qc = parse_sql(query, pattern_predicates=True) if isinstance(query, str) else query
         if key_space is not None and qc.expressions():
             raise ValueError(f"a query with arithmetic expressions ({', '.join(qc.expressions())}) takes no key_space: "
                              "the cross-rank merge does not cover it")

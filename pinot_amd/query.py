@@ -34,7 +34,9 @@ DEFAULT_NUM_GROUPS_LIMIT = 100_000   # InstancePlanMakerImplV2.DEFAULT_NUM_GROUP
 
 @dataclasses.dataclass(frozen=True)
 class Predicate:
-    """EQ / NOT_EQ / IN / NOT_IN / RANGE on one column (RangePredicate: None bound = UNBOUNDED)."""
+    """EQ / NOT_EQ / IN / NOT_IN / RANGE / REGEXP_LIKE on one column (RangePredicate: None bound = UNBOUNDED;
+    RegexpLikePredicate: values = (pattern,), case_insensitive = match parameter 'i'; a LIKE is the REGEXP_LIKE of
+    like_to_regexp's pattern with 'i')."""
     type: str
     column: str
     values: Tuple = ()
@@ -42,12 +44,13 @@ class Predicate:
     upper: object = None
     lower_inclusive: bool = True
     upper_inclusive: bool = True
+    case_insensitive: bool = False
 
     def negated(self) -> "Predicate":
         flip = {"EQ": "NOT_EQ", "NOT_EQ": "EQ", "IN": "NOT_IN", "NOT_IN": "IN"}
         if self.type in flip:
             return dataclasses.replace(self, type=flip[self.type])
-        raise NotImplementedError  # RANGE negation is represented with a negate flag
+        raise NotImplementedError  # RANGE / REGEXP_LIKE negation is represented with a negate flag
 
 
 @dataclasses.dataclass
@@ -114,8 +117,60 @@ def _literal_text(v) -> str:
     return v if isinstance(v, str) else repr(v)
 
 
+REGEXP_METACHARACTERS = "^$.{}[]()*+?|<>-&/"
+
+
+def like_to_regexp(like: str) -> str:
+    """RegexpPatternConverterUtils.likeToRegexpLike: the REGEXP_LIKE pattern of a LIKE pattern."""
+    start, end, prefix, suffix = 0, len(like), "^", "$"
+    if not like:
+        return "^$"
+    if len(like) == 1:
+        if like == "%":
+            return ""
+    else:
+        if like[0] == "%":
+            start = next((i for i, ch in enumerate(like) if ch != "%"), -1)
+            if start == -1:
+                return ""
+            prefix = ""
+        if like[-1] == "%":
+            end = max(i for i, ch in enumerate(like) if ch != "%") + 1
+            suffix = ""
+    out, prev_backslash = [prefix], False
+    for ch in like[start:end]:
+        if ch == "_":
+            out.append(ch if prev_backslash else ".")
+        elif ch == "%":
+            out.append(ch if prev_backslash else ".*")
+        else:
+            # a metacharacter, or a backslash that escaped no wildcard: escaped in the output
+            if ch in REGEXP_METACHARACTERS or prev_backslash:
+                out.append("\\")
+            out.append(ch)
+        prev_backslash = ch == "\\"
+    if prev_backslash:
+        out.append("\\")
+    return "".join(out) + suffix
+
+
+def regexp_case_insensitive(match_parameter: str) -> bool:
+    """RegexpPatternConverterUtils.isCaseInsensitive: '' / 'c' / 'C' -> False, 'i' / 'I' -> True."""
+    if not match_parameter:
+        return False
+    if len(match_parameter) != 1:
+        raise ValueError(f"REGEXP_LIKE: match parameter must be exactly one character, got {match_parameter!r}")
+    if match_parameter.lower() == "i":
+        return True
+    if match_parameter.lower() == "c":
+        return False
+    raise ValueError(f"REGEXP_LIKE: unsupported match parameter {match_parameter!r} (only 'i' and 'c')")
+
+
 def predicate_text(p: Predicate) -> str:
-    """EqPredicate / NotEqPredicate / InPredicate / NotInPredicate / RangePredicate.toString."""
+    """EqPredicate / NotEqPredicate / InPredicate / NotInPredicate / RangePredicate / RegexpLikePredicate.toString."""
+    if p.type == "REGEXP_LIKE":
+        return f"regexp_like({p.column},'{p.values[0]}'" + (",'i')" if p.case_insensitive else ")")
     if p.type in ("EQ", "NOT_EQ"):
         return f"{p.column} {'=' if p.type == 'EQ' else '!='} '{_literal_text(p.values[0])}'"
     if p.type in ("IN", "NOT_IN"):
@@ -627,9 +682,15 @@ def _tokenize(sql: str):
 
 
 class _Parser:
-    def __init__(self, sql: str):
+    def __init__(self, sql: str, pattern_predicates: bool = False):
         self.t = _tokenize(sql)
         self.i = 0
+        self.pattern_predicates = pattern_predicates
+
+    def need_pattern_predicates(self, what: str) -> None:
+        if not self.pattern_predicates:
+            raise ValueError(f"{what}: pattern predicates are not enabled for this parse "
+                             "(parse_sql(sql, pattern_predicates=True); ServerQueryExecutor enables them for SQL text)")
 
     def peek(self, k=0):
         return self.t[self.i + k] if self.i + k < len(self.t) else ("eof", None)
@@ -987,7 +1048,31 @@ class _Parser:
             self.i = start
         return self.comparison()
 
+    def regexp_like(self) -> FilterContext:
+        """REGEXP_LIKE(col, 'pattern'[, 'match parameter'])."""
+        self.i += 1
+        self.eat_op("(")
+        col = self.ident()
+        self.eat_op(",")
+        pat = self.peek()
+        if pat[0] != "str":
+            raise ValueError(f"REGEXP_LIKE: the pattern must be a string literal, got {pat}")
+        self.i += 1
+        ci = False
+        if self.peek() == ("op", ","):
+            self.i += 1
+            par = self.peek()
+            if par[0] != "str":
+                raise ValueError(f"REGEXP_LIKE: the match parameter must be a string literal, got {par}")
+            self.i += 1
+            ci = regexp_case_insensitive(par[1])
+        self.eat_op(")")
+        return FilterContext.pred(Predicate("REGEXP_LIKE", col, (pat[1],), case_insensitive=ci))
+
     def comparison(self) -> FilterContext:
+        if self.kw("REGEXP_LIKE") and self.peek(1) == ("op", "("):
+            self.need_pattern_predicates("REGEXP_LIKE")
+            return self.regexp_like()
         lhs = self.value_expr()
         if lhs[0] == "col":
             col = lhs[1]
@@ -1004,6 +1089,19 @@ class _Parser:
                 vals.append(self.literal())
             self.eat_op(")")
             return FilterContext.pred(Predicate("NOT_IN" if neg else "IN", col, tuple(vals)))
+        if self.kw("NOT", "LIKE") or self.kw("LIKE"):
+            # RequestContextUtils: LIKE is rewritten to REGEXP_LIKE(col, likeToRegexpLike(pattern), 'i')
+            self.need_pattern_predicates("LIKE")
+            neg = self.kw("NOT")
+            self.i += 2 if neg else 1
+            pat = self.peek()
+            if pat[0] != "str":
+                raise ValueError(f"LIKE: the pattern must be a string literal, got {pat}")
+            if lhs[0] != "col":
+                raise ValueError(f"LIKE on the expression {col}: a STRING column is needed")
+            self.i += 1
+            p = FilterContext.pred(Predicate("REGEXP_LIKE", col, (like_to_regexp(pat[1]),), case_insensitive=True))
+            return FilterContext.not_(p) if neg else p
         if self.kw("NOT", "BETWEEN") or self.kw("BETWEEN"):
             neg = self.kw("NOT")
             self.i += 2 if neg else 1
@@ -1061,30 +1159,35 @@ def _query_options(sql: str):
     return sql, opts
 
 
-_PARSED: "collections.OrderedDict[str, QueryContext]" = collections.OrderedDict()
+_PARSED: "collections.OrderedDict[tuple, QueryContext]" = collections.OrderedDict()
 
 
-def parse_sql(sql: str) -> QueryContext:
+def parse_sql(sql: str, pattern_predicates: bool = False) -> QueryContext:
     """Compile a Pinot SQL query of the supported subset into a QueryContext. The numGroupsLimit,
     minServerGroupTrimSize, groupTrimThreshold, serverReturnFinalResult, sortAggregateLimitThreshold and
     minSegmentGroupTrimSize query options (QueryOptionsUtils) are honoured; other options are ignored.
     A re-issued query text returns the QueryContext compiled the first time (256 most recent texts; the contexts
     are never mutated after parsing -- derived queries are dataclasses.replace copies): a configs[2] IN list of
-    18K literals took 30-80 ms to parse, longer than its device step."""
-    qc = _PARSED.get(sql)
+    18K literals took 30-80 ms to parse, longer than its device step.
+    pattern_predicates: accept [NOT] LIKE and [NOT] REGEXP_LIKE(col, 'p'[, 'i']) as REGEXP_LIKE predicates. Off by
+    default: a QueryContext also goes to consumers that know the five earlier predicate types only (the CPU oracle,
+    host-side mirrors), and for them such a query stays the ValueError it always was; ServerQueryExecutor, which
+    executes the predicates, turns it on for the SQL text it is given."""
+    key = (sql, bool(pattern_predicates))
+    qc = _PARSED.get(key)
     if qc is not None:
-        _PARSED.move_to_end(sql)
+        _PARSED.move_to_end(key)
         return qc
-    qc = _parse_sql(sql)
-    _PARSED[sql] = qc
+    qc = _parse_sql(sql, pattern_predicates)
+    _PARSED[key] = qc
     if len(_PARSED) > 256:
         _PARSED.popitem(last=False)
     return qc
 
 
-def _parse_sql(sql: str) -> QueryContext:
+def _parse_sql(sql: str, pattern_predicates: bool = False) -> QueryContext:
     sql, opts = _query_options(sql)
-    qc = _Parser(sql).query()
+    qc = _Parser(sql, pattern_predicates).query()
     for k, v in opts.items():
         if k.lower() == "numgroupslimit":
             qc.num_groups_limit = int(v)
