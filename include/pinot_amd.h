@@ -97,7 +97,14 @@ enum pinot_amd_agg_type { PINOT_AMD_AGG_COUNT = 0, PINOT_AMD_AGG_SUM = 1, PINOT_
                            * of values, count of values); MINMAXRANGEMV: the pair (min, max), final max - min. No
                            * matching doc: 0, 0.0, +inf, -inf, -inf, -inf. See "Multi-value columns" below. */
                           PINOT_AMD_AGG_COUNTMV = 11, PINOT_AMD_AGG_SUMMV = 12, PINOT_AMD_AGG_MINMV = 13,
-                          PINOT_AMD_AGG_MAXMV = 14, PINOT_AMD_AGG_AVGMV = 15, PINOT_AMD_AGG_MINMAXRANGEMV = 16 };
+                          PINOT_AMD_AGG_MAXMV = 14, PINOT_AMD_AGG_AVGMV = 15, PINOT_AMD_AGG_MINMAXRANGEMV = 16,
+                          /* DistinctCountHLLAggregationFunction.java over one single-value column: per group a
+                           * stream-lib HyperLogLog(log2m) offered every matching doc's value (MurmurHash.hash of the
+                           * boxed value; a dictionary column offers each distinct value once: the same registers);
+                           * merge = element-wise maximum of the registers, final = HyperLogLog.cardinality() as a
+                           * LONG, 0 without a matching doc. Registers and estimate equal Pinot's bit for bit. Added
+                           * with pinot_amd_query_add_aggregation_hll (it takes log2m). */
+                          PINOT_AMD_AGG_DISTINCTCOUNTHLL = 17 };
 
 /* ------------------------------------------------------------------------------------------------
  * Runtime
@@ -391,6 +398,12 @@ int pinot_amd_query_add_aggregation_param(pinot_amd_query* q, int32_t agg_type, 
  * before (EINVAL), so the *MV functions have their own. The aggregation may carry FILTER lanes
  * (pinot_amd_query_add_aggregation_filter_predicate) like its single-value counterpart. */
 int pinot_amd_query_add_aggregation_mv(pinot_amd_query* q, int32_t agg_type, const char* column, int32_t* out_index);
+/* DISTINCTCOUNTHLL(column [, log2m]) (DistinctCountHLLAggregationFunction's constructor: one column, an optional
+ * integer literal, CommonConstants.Helix.DEFAULT_HYPERLOGLOG_LOG2M = 8 without it). 4 <= log2m <= 16, anything else:
+ * EINVAL; NULL / "*" for the column: EINVAL; an arithmetic expression or a transformed key as the column:
+ * EUNSUPPORTED. The three entry points above refuse PINOT_AMD_AGG_DISTINCTCOUNTHLL (EINVAL). The aggregation takes no
+ * FILTER lanes and no multi-value column (EUNSUPPORTED at pinot_amd_execute, naming the column). */
+int pinot_amd_query_add_aggregation_hll(pinot_amd_query* q, const char* column, int32_t log2m, int32_t* out_index);
 /* Aggregation over a binary arithmetic transform of two columns (SUM / MIN / MAX / AVG):
  * MultiplicationTransformFunction (times), SubtractionTransformFunction (minus),
  * AdditionTransformFunction (plus) in core/operator/transform/function/. Pinot evaluates these in
@@ -648,6 +661,16 @@ int pinot_amd_result_fetch_value_counts(pinot_amd_result* r, int32_t agg_index, 
 /* String value of merged-dictionary id `id` of aggregation agg_index's value-set column (NULL when it is
  * not a STRING column or id is out of range). */
 const char* pinot_amd_result_distinct_string(pinot_amd_result* r, int32_t agg_index, int64_t id);
+
+/* The registers of aggregation agg_index, a PINOT_AMD_AGG_DISTINCTCOUNTHLL of the result: the intermediate result
+ * a server hands on (DistinctCountHLLAggregationFunction.extractAggregationResult / extractGroupByResult: the
+ * HyperLogLog itself; here its RegisterSet as one byte per register, 2^log2m per group, not the library's serialised
+ * form). Groups in pinot_amd_result_fetch's order (after a server table: its kept groups in its order);
+ * *out_log2m and *out_groups are always set; h_registers NULL: sizes only; fewer than groups << log2m bytes of
+ * capacity: EOVERFLOW. pinot_amd_result_fetch returns the estimate (exact in h_values_i64),
+ * pinot_amd_result_fetch_intermediate (estimate, 0). */
+int pinot_amd_result_fetch_hll(pinot_amd_result* r, int32_t agg_index, int64_t cap_bytes, uint8_t* h_registers,
+                               int32_t* out_log2m, int64_t* out_groups);
 
 /* Selection results (DataSchema + rows of SelectionResultsBlock). EINVAL on any other result. */
 int pinot_amd_result_selection_num_columns(pinot_amd_result* r, int32_t* h_out);

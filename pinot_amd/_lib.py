@@ -102,6 +102,7 @@ SIGNATURES = {
     "pinot_amd_query_add_aggregation_param": (C.c_int, [_P, C.c_int32, C.c_char_p, C.c_double,
                                                         C.POINTER(C.c_int32)]),
     "pinot_amd_query_add_aggregation_mv": (C.c_int, [_P, C.c_int32, C.c_char_p, C.POINTER(C.c_int32)]),
+    "pinot_amd_query_add_aggregation_hll": (C.c_int, [_P, C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
     "pinot_amd_query_set_num_groups_limit": (C.c_int, [_P, C.c_int64]),
     "pinot_amd_query_set_group_key_values": (C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int64, _I64P,
                                                        C.POINTER(C.c_double), C.POINTER(C.c_char_p)]),
@@ -122,6 +123,7 @@ SIGNATURES = {
     "pinot_amd_result_fetch_intermediate": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_double), _I64P]),
     "pinot_amd_result_string_key": (C.c_char_p, [_P, C.c_int32, C.c_int64]),
     "pinot_amd_result_fetch_distinct_values": (C.c_int, [_P, C.c_int32, C.c_int64, _I64P, _I64P, _I64P]),
+    "pinot_amd_result_fetch_hll": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(C.c_int32), _I64P]),
     "pinot_amd_result_fetch_value_counts": (C.c_int, [_P, C.c_int32, C.c_int64, _I64P, _I64P, _I64P, _I64P]),
     "pinot_amd_result_distinct_string": (C.c_char_p, [_P, C.c_int32, C.c_int64]),
     "pinot_amd_result_accumulators": (C.c_int, [_P, C.POINTER(C.c_int32), _I64P, _PP, C.POINTER(C.c_int32)]),

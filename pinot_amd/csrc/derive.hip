@@ -26,6 +26,8 @@
 #include "../../include/pinot_amd.h"
 #include "device_types.h"
 #include "kernels.h"
+#define PAMD_HLL_HD __host__ __device__
+#include "hll.h"
 
 namespace pamd {
 
@@ -676,6 +678,71 @@ __global__ void __launch_bounds__(kBlock) mv_reduce_kernel(DevMvColumn c, const 
       else atomicAdd(&out[d], x);
     }
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// DISTINCTCOUNTHLL twins (hll.h): per value the register index and the rank its hash sets
+// (HyperLogLog.offer = offerHashed(MurmurHash.hash(boxed value))). One lane per value; the values of a raw column as
+// staged (big-endian), a dictionary's as int64 / double in host order, a STRING dictionary's bytes and offsets as
+// dict_regex_match_kernel reads them. INT and FLOAT hash the sign-extended 32 stored bits, LONG and DOUBLE the 64.
+// ------------------------------------------------------------------------------------------------
+template <int SRC>
+__global__ void __launch_bounds__(256) hll_hash_kernel(const void* src_, const int32_t* offs_, int64_t n, int log2m,
+                                                       int32_t* idx_, int32_t* rank_) {
+  typedef __attribute__((address_space(1))) const uint32_t gu32;
+  typedef __attribute__((address_space(1))) const uint64_t gu64;
+  typedef __attribute__((address_space(1))) const uint8_t gu8;
+  typedef __attribute__((address_space(1))) const int32_t gi32;
+  typedef __attribute__((address_space(1))) int32_t go32;
+  go32* idx = (go32*)idx_;
+  go32* rank = (go32*)rank_;
+  for (int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; d < n; d += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t h;
+    if (SRC == HLL_SRC_BE32) {
+      h = hll_hash_value(HLL_INT, (uint64_t)__builtin_bswap32(((gu32*)src_)[d]));
+    } else if (SRC == HLL_SRC_BE64) {
+      const uint32_t hi = ((gu32*)src_)[2 * d], lo = ((gu32*)src_)[2 * d + 1];
+      h = hll_hash_value(HLL_LONG, ((uint64_t)__builtin_bswap32(hi) << 32) | __builtin_bswap32(lo));
+    } else if (SRC == HLL_SRC_LE64) {
+      h = hll_hash_value(HLL_LONG, ((gu64*)src_)[d]);
+    } else if (SRC == HLL_SRC_LE64_F32) {  // a FLOAT dictionary's values held as doubles: back to the float's bits
+      const float f = (float)__longlong_as_double((long long)((gu64*)src_)[d]);
+      h = hll_hash_value(HLL_FLOAT, (uint64_t)__float_as_uint(f));
+    } else {  // HLL_SRC_STRING: MurmurHash.hash(bytes, len, -1), the value ending at its first NUL
+      gi32* offs = (gi32*)offs_;
+      gu8* p = (gu8*)src_ + offs[d];
+      const int32_t cap = offs[d + 1] - offs[d];
+      int32_t len = 0;
+      while (len < cap && p[len] != 0) ++len;
+      h = hll_hash_bytes(p, len);
+    }
+    uint32_t j, r;
+    hll_index_rank(h, log2m, &j, &r);
+    idx[d] = (int32_t)j;
+    rank[d] = (int32_t)r;
+  }
+}
+
+// src: n values in the layout `src_kind` names (offs: the n + 1 byte offsets of HLL_SRC_STRING); idx / rank: n entries
+hipError_t launch_hll_hash(const void* src, const int32_t* offs, int src_kind, int64_t n, int log2m, int32_t* idx,
+                           int32_t* rank, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (log2m < kHllMinLog2m || log2m > kHllMaxLog2m || !src || !idx || !rank) return hipErrorInvalidValue;
+  const dim3 g(grid_of(n)), b(256);
+  switch (src_kind) {
+    case HLL_SRC_BE32: hipLaunchKernelGGL(hll_hash_kernel<HLL_SRC_BE32>, g, b, 0, st, src, offs, n, log2m, idx, rank); break;
+    case HLL_SRC_BE64: hipLaunchKernelGGL(hll_hash_kernel<HLL_SRC_BE64>, g, b, 0, st, src, offs, n, log2m, idx, rank); break;
+    case HLL_SRC_LE64: hipLaunchKernelGGL(hll_hash_kernel<HLL_SRC_LE64>, g, b, 0, st, src, offs, n, log2m, idx, rank); break;
+    case HLL_SRC_LE64_F32:
+      hipLaunchKernelGGL(hll_hash_kernel<HLL_SRC_LE64_F32>, g, b, 0, st, src, offs, n, log2m, idx, rank);
+      break;
+    case HLL_SRC_STRING:
+      if (!offs) return hipErrorInvalidValue;
+      hipLaunchKernelGGL(hll_hash_kernel<HLL_SRC_STRING>, g, b, 0, st, src, offs, n, log2m, idx, rank);
+      break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
 }
 
 __global__ void fill_u64_kernel(unsigned long long* p, int64_t n, unsigned long long x) {

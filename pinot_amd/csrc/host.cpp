@@ -30,6 +30,7 @@
 #include "../../include/pinot_amd.h"
 #include "device_types.h"
 #include "expr.h"
+#include "hll.h"
 #include "jit.h"
 #include "kernels.h"
 #include "regex_dfa.h"
@@ -1579,12 +1580,16 @@ struct AggSpec {
   std::string column;   // empty for COUNT(*); first operand of an expression
   int32_t expr = 0;     // pinot_amd_expr_op (PINOT_AMD_EXPR_COLUMN: the column itself)
   std::string column2;  // second operand of an expression
-  double param = 0;     // PINOT_AMD_AGG_PERCENTILE: the percentile (part of no plan's identity: the fold reads it)
+  double param = 0;     // PINOT_AMD_AGG_PERCENTILE: the percentile (part of no plan's identity: the fold reads it);
+                        // PINOT_AMD_AGG_DISTINCTCOUNTHLL: log2m (its register query's twin names carry it)
 };
 
 // the aggregations answered from a value-set query (execute_distinct): DISTINCTCOUNT, PERCENTILE, DISTINCTSUM,
 // DISTINCTAVG
 static bool is_value_set_agg(int32_t t) { return t >= PINOT_AMD_AGG_DISTINCTCOUNT && t <= PINOT_AMD_AGG_DISTINCTAVG; }
+// DISTINCTCOUNTHLL: answered by execute_distinct too, from a register query (AggSpec::param holds its log2m)
+static bool is_hll_agg(int32_t t) { return t == PINOT_AMD_AGG_DISTINCTCOUNTHLL; }
+static bool is_child_agg(int32_t t) { return is_value_set_agg(t) || is_hll_agg(t); }
 // the multi-value aggregations: planned over the single-value twins of the column's per-doc count / sum / min / max
 // (PlanBuild::raw_keys redirects AggSpec::column, and column2 for the two that read a second twin)
 static bool is_mv_agg(int32_t t) { return t >= PINOT_AMD_AGG_COUNTMV && t <= PINOT_AMD_AGG_MINMAXRANGEMV; }
@@ -1615,6 +1620,10 @@ struct pinot_amd_query {
   // identity, key caches, the value-set sub-queries' copies); twin name -> (source column, spec)
   struct KeyTransform { std::string column; DevKeyTransform tf; };
   std::map<std::string, KeyTransform> key_tf;
+  // DISTINCTCOUNTHLL's register query (execute_distinct) names the two twins of its column here, "<column>$hllidx<log2m>"
+  // and "<column>$hllrank<log2m>": twin name -> (source column, log2m). PlanBuild::raw_keys builds the ones a plan names
+  struct HllTwin { std::string column; int log2m; };
+  std::map<std::string, HllTwin> hll_tf;
   // arithmetic expressions (pinot_amd_query_define_expression): the virtual column's name -> its canonical tree. The
   // name stands wherever a column's does (predicates, GROUP BY, aggregations, selection), so it is part of everything
   // keyed by the query's text; PlanBuild::raw_keys gives every segment a raw DOUBLE twin under that name
@@ -1853,6 +1862,24 @@ int pinot_amd_query_add_aggregation_param(pinot_amd_query* q, int32_t agg_type, 
   return 0;
 }
 
+int pinot_amd_query_add_aggregation_hll(pinot_amd_query* q, const char* column, int32_t log2m, int32_t* out_index) {
+  if (!q) return fail(PINOT_AMD_EINVAL, "add_aggregation_hll: null query");
+  if (!column || !*column || strcmp(column, "*") == 0) return fail(PINOT_AMD_EINVAL, "add_aggregation_hll: column required");
+  if (log2m < kHllMinLog2m || log2m > kHllMaxLog2m)
+    return fail(PINOT_AMD_EINVAL, "add_aggregation_hll: DISTINCTCOUNTHLL(%s, %d): log2m must be %d to %d", column, log2m,
+                kHllMinLog2m, kHllMaxLog2m);
+  if (q->exprs.count(column))
+    return fail(PINOT_AMD_EUNSUPPORTED, "add_aggregation_hll: DISTINCTCOUNTHLL of the expression %s (the sketch hashes a "
+                                        "column's stored values)", column);
+  if (q->key_tf.count(column))
+    return fail(PINOT_AMD_EUNSUPPORTED, "add_aggregation_hll: DISTINCTCOUNTHLL of the transformed key %s", column);
+  AggSpec a{PINOT_AMD_AGG_DISTINCTCOUNTHLL, column};
+  a.param = (double)log2m;
+  if (out_index) *out_index = (int32_t)q->aggs.size();
+  q->aggs.push_back(a);
+  return 0;
+}
+
 int pinot_amd_query_add_aggregation_mv(pinot_amd_query* q, int32_t agg_type, const char* column, int32_t* out_index) {
   if (!q) return fail(PINOT_AMD_EINVAL, "add_aggregation_mv: null query");
   if (!is_mv_agg(agg_type)) return fail(PINOT_AMD_EINVAL, "add_aggregation_mv: %d is no multi-value aggregation", agg_type);
@@ -2072,6 +2099,13 @@ struct DistinctFold {
     DevBuf ccount, scount, cum, bsum, pct, pid, dictd, dicti, sumd, sumi, partd, parti;
     std::vector<int64_t> h_cnts;  // scount on the host, with h_vals
     bool h_cnts_valid = false;
+    // a DISTINCTCOUNTHLL register query (log2m > 0): grouped by (g..., c$hllidx<log2m>), MAX(c$hllrank<log2m>). The
+    // fold places its rows' ranks in regs (nbase << log2m bytes, one per register; the result owns it and
+    // execute_again reuses it) and reduces them to est (per group S and the zero registers: hll_estimate's inputs),
+    // which land in the group's host row at sum_word. cacc: the rows' exported accumulators
+    int log2m = 0;
+    DevBuf regs, est, cacc, bad;
+    std::vector<uint8_t> h_regs;  // regs on the host (pinot_amd_result_fetch_hll), valid with h_valid
   };
   std::deque<Child> children;
   std::vector<AggSpec> aggs;       // the caller's aggregations
@@ -2927,10 +2961,11 @@ static int make_leaf_for_segment(pinot_amd_result* r, int si, pinot_amd_segment*
 // column: same groups, same key values, same dense mixed-radix key space.
 // the last step of a derived twin: the docs' dictIds (device, nd entries) packed fixed-bit, the dictionary
 // (device, big-endian values of `type`, `card` of them) copied out, and both staged as column `name`
+// (dict_always: the dictionary is copied for a segment without docs too)
 static int stage_derived_twin(pinot_amd_segment* s, const std::string& name, int type, int64_t nd, const DevBuf& ids,
-                              const DevBuf& dict_be, int64_t card) {
+                              const DevBuf& dict_be, int64_t card, bool dict_always = false) {
   const int vs = value_size(type);
-  const bool have = nd > 0 && card > 0;
+  const bool have = (nd > 0 || dict_always) && card > 0;
   card = std::max<int64_t>(card, 1);
   int bits = 1;
   while (card > 1 && (1ll << bits) < card) ++bits;  // PinotDataBitSet.getNumBitsPerValue(card - 1)
@@ -3012,6 +3047,93 @@ static int derive_transform_twin(pinot_amd_segment* s, const std::string& col, c
     }
   }
   return stage_derived_twin(s, twin, T_LONG, nd, nd > 0 ? doc_ids : ids, dict_be, card);
+}
+
+static std::string hll_twin_name(const std::string& col, int log2m, bool rank) {
+  return col + (rank ? "$hllrank" : "$hllidx") + std::to_string(log2m);
+}
+
+// what DISTINCTCOUNTHLL cannot read, over the whole batch and before anything is built (a refusal stages nothing)
+static int check_hll_source(pinot_amd_segment* const* segs, int32_t n, const std::string& col) {
+  for (int32_t i = 0; i < n; ++i) {
+    if (!segs[i]) return fail(PINOT_AMD_EINVAL, "execute: null segment");
+    auto it = segs[i]->cols.find(col);
+    if (it == segs[i]->cols.end())
+      return fail(PINOT_AMD_EINVAL, "segment %s has no column %s", segs[i]->name.c_str(), col.c_str());
+    const Column& c = *it->second;
+    if (c.mv) return fail(PINOT_AMD_EUNSUPPORTED, "DISTINCTCOUNTHLL of multi-value column %s", col.c_str());
+    if (c.type < T_INT || c.type > T_STRING)
+      return fail(PINOT_AMD_EUNSUPPORTED, "DISTINCTCOUNTHLL of column %s of stored type %d (serialised sketches in BYTES "
+                                          "columns are not read)", col.c_str(), c.type);
+    if (c.type == T_STRING && c.enc == ENC_RAW)
+      return fail(PINOT_AMD_EUNSUPPORTED, "DISTINCTCOUNTHLL of raw STRING column %s", col.c_str());
+    if (c.type != segs[0]->cols.at(col)->type)
+      return fail(PINOT_AMD_EINVAL, "column %s has different types across segments", col.c_str());
+  }
+  return 0;
+}
+
+// DISTINCTCOUNTHLL(col, log2m): the segment gets, once, the two twins of the register query -- per doc the register
+// index its value's hash selects ("<col>$hllidx<log2m>", identity INT dictionary 0 .. m - 1, log2m bits) and the rank
+// it sets ("<col>$hllrank<log2m>", identity INT dictionary 0 .. 33 - log2m, 5 bits), hll_hash_kernel's outputs. The
+// identity dictionaries make dictId = value and every segment's key space the same. Routes as derive_transform_twin:
+// a raw column hashes its staged values, a dictionary-encoded or sorted one its dictionary's (the STRING bytes as the
+// pattern predicates stage them) and maps the docs through the two tables. Both twins are staged last.
+static int derive_hll_twins(pinot_amd_segment* s, const std::string& col, int log2m) {
+  const std::string tidx = hll_twin_name(col, log2m, false), trank = hll_twin_name(col, log2m, true);
+  const bool have_idx = s->cols.count(tidx), have_rank = s->cols.count(trank);
+  if (have_idx && have_rank) return 0;
+  const Column& c = *s->cols.at(col);
+  const int64_t nd = s->num_docs;
+  const bool raw = c.enc == ENC_RAW;
+  const int64_t items = raw ? nd : c.type == T_STRING ? (int64_t)c.dict_s.size()
+                                   : is_float(c.type) ? (int64_t)c.dict_d.size() : (int64_t)c.dict_i.size();
+  if (!raw && nd > 0 && items < 1) return fail(PINOT_AMD_EINVAL, "column %s: empty dictionary", col.c_str());
+  const int64_t m = (int64_t)1 << log2m, nranks = 34 - log2m;
+  DevBuf hidx, hrank, src, didx, drank, dict_idx, dict_rank;
+  if (int rc = hidx.alloc((size_t)std::max<int64_t>(items, 1) * 4)) return rc;
+  if (int rc = hrank.alloc((size_t)std::max<int64_t>(items, 1) * 4)) return rc;
+  if (nd > 0) {
+    if (raw) {
+      const int kind = (c.type == T_INT || c.type == T_FLOAT) ? HLL_SRC_BE32 : HLL_SRC_BE64;
+      HIP_OK(launch_hll_hash(c.fwd.p, nullptr, kind, nd, log2m, (int32_t*)hidx.p, (int32_t*)hrank.p, nullptr));
+    } else {
+      if (c.type == T_STRING) {
+        bool have = false;
+        if (int rc = string_dict_device(s, c, &have)) return rc;
+        if (!have) return fail(PINOT_AMD_EUNSUPPORTED, "DISTINCTCOUNTHLL(%s): the STRING dictionary exceeds 2 GiB", col.c_str());
+        HIP_OK(launch_hll_hash(c.sdict_bytes.p, (const int32_t*)c.sdict_offs.p, HLL_SRC_STRING, items, log2m,
+                               (int32_t*)hidx.p, (int32_t*)hrank.p, nullptr));
+      } else {
+        const void* hv = is_float(c.type) ? (const void*)c.dict_d.data() : (const void*)c.dict_i.data();
+        if (int rc = src.alloc_copy(hv, (size_t)items * 8, 64)) return rc;
+        HIP_OK(launch_hll_hash(src.p, nullptr, c.type == T_FLOAT ? HLL_SRC_LE64_F32 : HLL_SRC_LE64, items, log2m,
+                               (int32_t*)hidx.p, (int32_t*)hrank.p, nullptr));
+      }
+      if (int rc = didx.alloc((size_t)nd * 4)) return rc;
+      if (int rc = drank.alloc((size_t)nd * 4)) return rc;
+      if (c.enc == ENC_SORTED) {
+        HIP_OK(launch_sorted_dict_ids((const int32_t*)c.fwd.p, items, nd, (const int32_t*)hidx.p, (int32_t*)didx.p, nullptr));
+        HIP_OK(launch_sorted_dict_ids((const int32_t*)c.fwd.p, items, nd, (const int32_t*)hrank.p, (int32_t*)drank.p, nullptr));
+      } else {
+        HIP_OK(launch_read_dict_ids((const uint8_t*)c.fwd.p, c.bits, 0, nd, (int32_t*)didx.p, nullptr));
+        HIP_OK(hipMemcpyAsync(drank.p, didx.p, (size_t)nd * 4, hipMemcpyDeviceToDevice, nullptr));
+        HIP_OK(launch_remap_dict_ids((int32_t*)didx.p, nd, (const int32_t*)hidx.p, items, nullptr));
+        HIP_OK(launch_remap_dict_ids((int32_t*)drank.p, nd, (const int32_t*)hrank.p, items, nullptr));
+      }
+    }
+  }
+  // the identity dictionaries, big-endian INT as staged dictionaries are
+  std::vector<uint32_t> ident((size_t)std::max(m, nranks));
+  for (size_t i = 0; i < ident.size(); ++i) ident[i] = __builtin_bswap32((uint32_t)i);
+  if (int rc = dict_idx.alloc_copy(ident.data(), (size_t)m * 4, 64)) return rc;
+  if (int rc = dict_rank.alloc_copy(ident.data(), (size_t)nranks * 4, 64)) return rc;
+  const bool through = raw || nd == 0;
+  if (!have_idx)
+    if (int rc = stage_derived_twin(s, tidx, T_INT, nd, through ? hidx : didx, dict_idx, m, true)) return rc;
+  if (!have_rank)
+    if (int rc = stage_derived_twin(s, trank, T_INT, nd, through ? hrank : drank, dict_rank, nranks, true)) return rc;
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4389,6 +4511,27 @@ int PlanBuild::raw_keys() {
       for (auto* s : segs) {
         const uint64_t gen0 = s->gen;
         if (int rc = derive_expr_twin(s, *e, r)) return rc;
+        restaged |= s->gen != gen0;
+      }
+  }
+  // DISTINCTCOUNTHLL's register query names its column's twins (execute_distinct); every segment gets the pair
+  if (!Qp->hll_tf.empty()) {
+    std::vector<const pinot_amd_query::HllTwin*> used;
+    auto note = [&](const std::string& name) {
+      auto it = Qp->hll_tf.find(name);
+      if (it == Qp->hll_tf.end()) return;
+      for (const auto* u : used)
+        if (u->column == it->second.column && u->log2m == it->second.log2m) return;
+      used.push_back(&it->second);
+    };
+    for (const std::string& g : Qp->group_by) note(g);
+    for (const AggSpec& a : Qp->aggs) note(a.column);
+    for (const auto* u : used)
+      if (int rc = check_hll_source(segs.data(), n, u->column)) return rc;
+    for (const auto* u : used)
+      for (auto* s : segs) {
+        const uint64_t gen0 = s->gen;
+        if (int rc = derive_hll_twins(s, u->column, u->log2m)) return rc;
         restaged |= s->gen != gen0;
       }
   }
@@ -6709,8 +6852,23 @@ static int execute_distinct(pinot_amd_query* qq, pinot_amd_segment* const* segs_
   auto fold = std::make_unique<DistinctFold>();
   std::vector<int32_t> base_index(U.aggs.size(), -1);
   std::vector<std::string> child_cols;
+  std::vector<int> child_log2m;  // 0: a value-set query, else the register query of DISTINCTCOUNTHLL(column, log2m)
   for (size_t a = 0; a < U.aggs.size(); ++a) {
     const AggSpec& A = U.aggs[a];
+    if (is_hll_agg(A.type)) {  // (of a GROUP BY column too: its sketch is hashed like any other)
+      const int log2m = (int)A.param;
+      if (U.exprs.count(A.column) || U.key_tf.count(A.column))
+        return fail(PINOT_AMD_EUNSUPPORTED, "DISTINCTCOUNTHLL of the expression or transformed key %s", A.column.c_str());
+      if (int rc = check_hll_source(segs_in, n, A.column)) return rc;
+      size_t k = 0;
+      while (k < child_cols.size() && !(child_cols[k] == A.column && child_log2m[k] == log2m)) ++k;
+      if (k == child_cols.size()) {
+        child_cols.push_back(A.column);
+        child_log2m.push_back(log2m);
+      }
+      fold->agg_child.push_back((int32_t)k);
+      continue;
+    }
     if (!is_value_set_agg(A.type)) {
       base_index[a] = (int32_t)base.aggs.size();
       base.aggs.push_back(A);
@@ -6728,12 +6886,13 @@ static int execute_distinct(pinot_amd_query* qq, pinot_amd_segment* const* segs_
       fold->agg_child.push_back(-2 - (int32_t)(g - U.group_by.begin()));
       continue;
     }
-    auto c = std::find(child_cols.begin(), child_cols.end(), A.column);
-    if (c == child_cols.end()) {
+    size_t c = 0;
+    while (c < child_cols.size() && !(child_cols[c] == A.column && child_log2m[c] == 0)) ++c;
+    if (c == child_cols.size()) {
       child_cols.push_back(A.column);
-      c = child_cols.end() - 1;
+      child_log2m.push_back(0);
     }
-    fold->agg_child.push_back((int32_t)(c - child_cols.begin()));
+    fold->agg_child.push_back((int32_t)c);
   }
   if (base.aggs.empty()) base.aggs.push_back(AggSpec{PINOT_AMD_AGG_COUNT, ""});
   if (!child_cols.empty() && U.group_by.size() >= (size_t)kMaxGroupCols)
@@ -6742,15 +6901,33 @@ static int execute_distinct(pinot_amd_query* qq, pinot_amd_segment* const* segs_
   pinot_amd_result* rb = nullptr;
   if (int rc = execute_impl(&base, segs_in, n, stream, false, &rb)) return rc;
   std::unique_ptr<pinot_amd_result, int (*)(pinot_amd_result*)> hold(rb, pinot_amd_result_destroy);
-  for (const std::string& col : child_cols) {
+  std::vector<uint64_t> gen0;
+  for (int32_t i = 0; i < n; ++i) gen0.push_back(segs_in[i] ? segs_in[i]->gen : 0);
+  for (size_t k = 0; k < child_cols.size(); ++k) {
+    const std::string& col = child_cols[k];
     pinot_amd_query cq = base;
-    cq.group_by.push_back(col);
-    cq.aggs.assign(1, AggSpec{PINOT_AMD_AGG_COUNT, ""});
+    if (child_log2m[k]) {  // the register query: GROUP BY (g..., index twin), MAX(rank twin); raw_keys builds the twins
+      const std::string tidx = hll_twin_name(col, child_log2m[k], false), trank = hll_twin_name(col, child_log2m[k], true);
+      cq.hll_tf[tidx] = {col, child_log2m[k]};
+      cq.hll_tf[trank] = {col, child_log2m[k]};
+      cq.group_by.push_back(tidx);
+      cq.aggs.assign(1, AggSpec{PINOT_AMD_AGG_MAX, trank});
+    } else {
+      cq.group_by.push_back(col);
+      cq.aggs.assign(1, AggSpec{PINOT_AMD_AGG_COUNT, ""});
+    }
     cq.num_groups_limit = (int64_t)1 << 30;
     fold->children.emplace_back();
     DistinctFold::Child& C = fold->children.back();
     C.column = col;
+    C.log2m = child_log2m[k];
     if (int rc = execute_impl(&cq, segs_in, n, stream, false, &C.r)) return rc;  // (fold's destructor frees the others)
+  }
+  {  // twins staged for a register query moved the segments' generations: the base is kept under the identity the
+     // re-issued query will compute
+    bool moved = false;
+    for (int32_t i = 0; i < n; ++i) moved |= segs_in[i]->gen != gen0[(size_t)i];
+    if (moved) rb->plan_key = plan_identity(base, std::vector<pinot_amd_segment*>(segs_in, segs_in + n), false);
   }
   // the words the fold appends to a group's host row after the children's distinct counts: per PERCENTILE the
   // selected value's merged-dictionary id; per child with a DISTINCTSUM / DISTINCTAVG its sum (two words, shared);
@@ -6759,6 +6936,15 @@ static int execute_distinct(pinot_amd_query* qq, pinot_amd_segment* const* segs_
   fold->agg_word.assign(U.aggs.size(), -1);
   for (size_t a = 0; a < U.aggs.size(); ++a) {
     const int32_t t = U.aggs[a].type, k = fold->agg_child[a];
+    if (is_hll_agg(t)) {  // S and the zero registers, shared by the aggregations of one register query
+      DistinctFold::Child& C = fold->children[(size_t)k];
+      if (C.sum_word < 0) {
+        C.sum_word = fold->nextra;
+        fold->nextra += 2;
+      }
+      fold->agg_word[a] = C.sum_word;
+      continue;
+    }
     if (t != PINOT_AMD_AGG_PERCENTILE && t != PINOT_AMD_AGG_DISTINCTSUM && t != PINOT_AMD_AGG_DISTINCTAVG) continue;
     if (k < 0 || t == PINOT_AMD_AGG_PERCENTILE) {
       fold->agg_word[a] = fold->nextra++;
@@ -6814,12 +7000,12 @@ int pinot_amd_execute(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, in
                       pinot_amd_result** out) {
   if (qq && qq->filtered())
     for (size_t ai = 0; ai < qq->aggs.size(); ++ai)
-      if (is_value_set_agg(qq->aggs[ai].type))
+      if (is_child_agg(qq->aggs[ai].type))
         return fail(PINOT_AMD_EUNSUPPORTED, "%s: the value-set queries of DISTINCTCOUNT / PERCENTILE / DISTINCTSUM / "
-                                            "DISTINCTAVG do not take the lanes' predicates",
+                                            "DISTINCTAVG / DISTINCTCOUNTHLL do not take the lanes' predicates",
                     qq->filter_of(ai) ? "FILTER on a value-set aggregation" : "filtered aggregations beside a value-set aggregation");
   if (qq && std::any_of(qq->aggs.begin(), qq->aggs.end(),
-                        [](const AggSpec& a) { return is_value_set_agg(a.type); }))
+                        [](const AggSpec& a) { return is_child_agg(a.type); }))
     return no_throw("execute", [&] { return execute_distinct(qq, segs_in, n, stream, out); });
   return no_throw("execute", [&] { return execute_impl(qq, segs_in, n, stream, false, out); });
 }
@@ -7154,7 +7340,9 @@ static std::string kernel_info_of(pinot_amd_result* r) {
   if (r->nlanes > 1)  // filtered aggregations: the filter lanes and the table their scan aggregates into
     info += " +lanes(" + std::to_string(r->nlanes - 1) + ") table=" + r->lane_table;
   if (r->dc)  // the plan that served each DISTINCTCOUNT column's value sets
-    for (DistinctFold::Child& ch : r->dc->children) info += " +distinct(" + ch.column + ":" + kernel_info_of(ch.r) + ")";
+    for (DistinctFold::Child& ch : r->dc->children)
+      info += (ch.log2m ? " +hll(" + ch.column + "," + std::to_string(ch.log2m) : " +distinct(" + ch.column) + ":" +
+              kernel_info_of(ch.r) + ")";
   return info;
 }
 
@@ -7267,7 +7455,7 @@ static int server_trim(pinot_amd_result* r);
 static int distinct_fold(pinot_amd_result* r, const uint64_t* d_hash_keys, int64_t ng);
 
 // words of a group's host row (cacc): its accumulators; a value-set result appends each value-set query's distinct
-// count, the words of its PERCENTILE / DISTINCTSUM / DISTINCTAVG aggregations (DistinctFold::agg_word) and the
+// count, the words of its PERCENTILE / DISTINCTSUM / DISTINCTAVG / DISTINCTCOUNTHLL aggregations (DistinctFold::agg_word) and the
 // group's index before the server table reorders the rows (the CSR's row)
 static int cacc_stride(const pinot_amd_result* r) {
   return std::max(r->q.nacc, 1) + (r->dc ? (int)r->dc->children.size() + r->dc->nextra + 1 : 0);
@@ -7381,6 +7569,13 @@ static void final_value(const pinot_amd_result* r, const uint64_t* A, int a, dou
   if (r->agg_type[a] == PINOT_AMD_AGG_DISTINCTCOUNT) {
     // the set's size: the fold's count in the group's row, or 1 for a GROUP BY column (its key's own value)
     *vi_out = r->agg_acc[a] < 0 ? 1 : (int64_t)A[r->agg_acc[a]];
+    *v_out = (double)*vi_out;
+    return;
+  }
+  if (is_hll_agg(r->agg_type[a])) {  // HyperLogLog.cardinality() from the fold's two words (hll.h)
+    const DistinctFold& D = *r->dc;
+    const uint64_t* X = A + std::max(r->q.nacc, 1) + (int)D.children.size() + D.agg_word[(size_t)a];
+    *vi_out = hll_estimate(X[0], X[1], D.children[(size_t)D.agg_child[(size_t)a]].log2m);
     *v_out = (double)*vi_out;
     return;
   }
@@ -7944,6 +8139,35 @@ static int distinct_fold(pinot_amd_result* r, const uint64_t* d_hash_keys, int64
     if (int rc = key_pack(c, &kc)) return rc;
     if (kc.ncols != r->num_group_by + 1 || (c->kind == PLAN_HASH && kc.nw != c->nw))
       return fail(PINOT_AMD_EINVAL, "DISTINCTCOUNT(%s): key packing mismatch", C.column.c_str());
+    if (C.log2m) {  // a register query: place the rows' ranks, reduce each group's registers
+      if (ng >= ((int64_t)1 << (31 - C.log2m)))
+        return fail(PINOT_AMD_EUNSUPPORTED, "DISTINCTCOUNTHLL(%s, %d): %lld groups of %d registers exceed 2^31 bytes",
+                    C.column.c_str(), C.log2m, (long long)ng, 1 << C.log2m);
+      if (kc.size[kc.ncols - 1] != (int64_t)1 << C.log2m)
+        return fail(PINOT_AMD_EINVAL, "DISTINCTCOUNTHLL(%s): the register key space holds %lld ids", C.column.c_str(),
+                    (long long)kc.size[kc.ncols - 1]);
+      const int cn = std::max(c->q.nacc, 1), aw = c->agg_acc[0];
+      if (aw < 0 || aw >= cn) return fail(PINOT_AMD_EINVAL, "DISTINCTCOUNTHLL(%s): no MAX accumulator", C.column.c_str());
+      if (int rc = C.regs.ensure(std::max<size_t>((size_t)ng << C.log2m, 8))) return rc;
+      if (int rc = C.est.ensure(std::max<size_t>((size_t)ng * 16, 16))) return rc;
+      if (int rc = C.miss.ensure(8)) return rc;
+      if (int rc = C.bad.ensure(8)) return rc;
+      if (nrows > 0) {
+        if (int rc = C.ckeys.ensure((size_t)nrows * kc.nw * 8)) return rc;
+        if (int rc = C.cacc.ensure((size_t)nrows * cn * 8)) return rc;
+        HIP_OK(launch_export_groups((const int32_t*)c->c_idx.p, nrows, T.keys, T.slots, T.acc, cn, kc, (uint64_t*)C.ckeys.p,
+                                    (uint64_t*)C.cacc.p, st));
+      }
+      HIP_OK(launch_hll_fold((const uint64_t*)C.ckeys.p, (const uint64_t*)C.cacc.p, cn, aw, nrows, kc, kb, bkeys, ng, C.log2m,
+                             (uint8_t*)C.regs.p, (unsigned long long*)C.est.p, (unsigned long long*)C.miss.p,
+                             (unsigned long long*)C.bad.p, st));
+      hsumi[(size_t)k].assign((size_t)ng * 2 + 1, 0);
+      if (ng > 0) HIP_OK(hipMemcpyAsync(hsumi[(size_t)k].data(), C.est.p, (size_t)ng * 16, hipMemcpyDeviceToHost, st));
+      HIP_OK(hipMemcpyAsync(&hsumi[(size_t)k][(size_t)ng * 2], C.bad.p, 8, hipMemcpyDeviceToHost, st));
+      HIP_OK(hipMemcpyAsync(&hmiss[(size_t)k], C.miss.p, 8, hipMemcpyDeviceToHost, st));
+      hcnt[(size_t)k].assign((size_t)ng, 0);
+      continue;
+    }
     C.cbits = bits_for(kc.size[kc.ncols - 1]);
     if (int rc = C.cnt.ensure((size_t)(ng + 1) * 4)) return rc;
     if (int rc = C.off.ensure((size_t)(ng + 1) * 8)) return rc;
@@ -8032,9 +8256,18 @@ static int distinct_fold(pinot_amd_result* r, const uint64_t* d_hash_keys, int64
     for (int k = 0; k < nch; ++k) rows[(size_t)g * S + nacc + k] = hcnt[(size_t)k][(size_t)g];
     rows[(size_t)g * S + S - 1] = (uint64_t)g;
   }
-  // the PERCENTILE / DISTINCTSUM / DISTINCTAVG words (DistinctFold::agg_word), read by final_value
+  // the PERCENTILE / DISTINCTSUM / DISTINCTAVG / DISTINCTCOUNTHLL words (DistinctFold::agg_word), read by final_value
   for (int k = 0; k < nch; ++k) {
     const DistinctFold::Child& C = D.children[(size_t)k];
+    if (C.log2m) {
+      if (hsumi[(size_t)k][(size_t)ng * 2] != 0)
+        return fail(PINOT_AMD_EINVAL, "DISTINCTCOUNTHLL(%s): %llu rows of the register query lie outside the sketch; the "
+                                      "result is void", C.column.c_str(), (unsigned long long)hsumi[(size_t)k][(size_t)ng * 2]);
+      if (C.sum_word >= 0)
+        for (int64_t g = 0; g < ng; ++g)
+          std::copy_n(&hsumi[(size_t)k][(size_t)g * 2], 2, &rows[(size_t)g * S + nacc + nch + C.sum_word]);
+      continue;
+    }
     const int np = (int)C.pct_aggs.size();
     for (int j = 0; j < np; ++j) {
       const int w = nacc + nch + D.agg_word[(size_t)C.pct_aggs[(size_t)j]];
@@ -8075,7 +8308,7 @@ static const MergedKeyColumn* distinct_dictionary(const pinot_amd_result* r, int
   if (!r || !r->dc || agg_index < 0 || agg_index >= (int32_t)r->dc->agg_child.size()) return nullptr;
   const int32_t k = r->dc->agg_child[(size_t)agg_index];
   if (k == -1) return nullptr;
-  if (k >= 0) return r->dc->children[(size_t)k].r->keys.back().get();
+  if (k >= 0) return r->dc->children[(size_t)k].log2m ? nullptr : r->dc->children[(size_t)k].r->keys.back().get();
   return r->keys[(size_t)(-2 - k)].get();
 }
 
@@ -8152,6 +8385,39 @@ static int fetch_value_csr(const char* what, bool with_counts, pinot_amd_result*
         if (with_counts) h_counts[o] = C.h_cnts[(size_t)i];
         h_values[o++] = encode(C.h_vals[(size_t)i]);
       }
+    }
+    return 0;
+  });
+}
+
+int pinot_amd_result_fetch_hll(pinot_amd_result* r, int32_t agg_index, int64_t cap_bytes, uint8_t* h_registers,
+                               int32_t* out_log2m, int64_t* out_groups) {
+  if (!r || cap_bytes < 0 || !out_log2m || !out_groups) return fail(PINOT_AMD_EINVAL, "fetch_hll: bad arguments");
+  if (!r->dc || agg_index < 0 || agg_index >= (int32_t)r->agg_type.size() || !is_hll_agg(r->agg_type[(size_t)agg_index]))
+    return fail(PINOT_AMD_EINVAL, "fetch_hll: aggregation %d is not a DISTINCTCOUNTHLL of this result", agg_index);
+  return no_throw("fetch_hll", [&]() -> int {
+    DistinctFold& D = *r->dc;
+    DistinctFold::Child& C = D.children[(size_t)D.agg_child[(size_t)agg_index]];
+    if (int rc = compact_groups(r)) return rc;
+    const int S = cacc_stride(r);
+    const int64_t ng = r->ngroups, m = (int64_t)1 << C.log2m;
+    *out_log2m = C.log2m;
+    *out_groups = ng;
+    if (!h_registers) return 0;  // sizing call
+    if (ng * m > cap_bytes)
+      return fail(PINOT_AMD_EOVERFLOW, "fetch_hll: %lld bytes exceed capacity %lld", (long long)(ng * m), (long long)cap_bytes);
+    if (!C.h_valid) {  // the registers of the groups before the server table, once per execution
+      C.h_regs.assign((size_t)(D.nbase * m), 0);
+      if (!C.h_regs.empty()) {
+        HIP_OK(hipMemcpyAsync(C.h_regs.data(), C.regs.p, C.h_regs.size(), hipMemcpyDeviceToHost, r->stream));
+        HIP_OK(hipStreamSynchronize(r->stream));
+      }
+      C.h_valid = true;
+    }
+    for (int64_t g = 0; g < ng; ++g) {  // the rows the server table kept, in its order
+      const int64_t src = (int64_t)r->cacc[(size_t)g * S + S - 1];
+      if (src < 0 || src >= D.nbase) return fail(PINOT_AMD_EINVAL, "fetch_hll: inconsistent group rows");
+      memcpy(h_registers + g * m, &C.h_regs[(size_t)(src * m)], (size_t)m);
     }
     return 0;
   });

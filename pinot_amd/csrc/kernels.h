@@ -54,6 +54,10 @@ hipError_t launch_merge_rows(const uint64_t* keys, const uint64_t* acc, int64_t 
 hipError_t launch_distinct_fold_count(const uint64_t* ckeys, int64_t nrows, const DevKeyPack& kc, const DevKeyPack& kb,
                                       const uint64_t* bkeys, int64_t nbase, int cbits, uint32_t* cnt, uint64_t* pair,
                                       unsigned long long* miss, hipStream_t st);
+hipError_t launch_hll_fold(const uint64_t* ckeys, const uint64_t* cacc, int nacc, int acc_word, int64_t nrows,
+                           const DevKeyPack& kc, const DevKeyPack& kb, const uint64_t* bkeys, int64_t nbase, int log2m,
+                           uint8_t* regs, unsigned long long* sz, unsigned long long* miss, unsigned long long* bad,
+                           hipStream_t st);
 hipError_t launch_distinct_fold_fill(const uint64_t* sorted, int64_t nrows, int cbits, const uint32_t* cnt, int64_t nbase,
                                      int64_t* off, int32_t* values, hipStream_t st);
 hipError_t launch_value_count_scan(const uint64_t* counts, int64_t n, int64_t* bsum, int64_t* cum, hipStream_t st);
@@ -129,6 +133,13 @@ hipError_t derive_dictionary(const uint8_t* d_src, int type, int src, const DevK
 hipError_t launch_remap_dict_ids(int32_t* ids, int64_t n, const int32_t* map, int64_t card, hipStream_t st);
 hipError_t launch_sorted_dict_ids(const int32_t* starts, int64_t card, int64_t n, const int32_t* map, int32_t* ids,
                                   hipStream_t st);
+// DISTINCTCOUNTHLL twins (hll_hash_kernel): how the n values to hash are stored
+enum HllSource { HLL_SRC_BE32 = 0 /* staged raw INT / FLOAT */, HLL_SRC_BE64 = 1 /* staged raw LONG / DOUBLE */,
+                 HLL_SRC_LE64 = 2 /* an INT / LONG dictionary as int64, a DOUBLE one as doubles, host order */,
+                 HLL_SRC_LE64_F32 = 3 /* a FLOAT dictionary as doubles */,
+                 HLL_SRC_STRING = 4 /* a STRING dictionary's bytes, offs its n + 1 byte offsets */ };
+hipError_t launch_hll_hash(const void* src, const int32_t* offs, int src_kind, int64_t n, int log2m, int32_t* idx,
+                           int32_t* rank, hipStream_t st);
 // Multi-value columns. A staged dictionary-encoded MV forward index (FixedBitMVForwardIndexWriter's file, all
 // big-endian): `words` is the 4-byte aligned file; the start-bit bitmap begins at dword bm_word0 (MSB-first, bit i
 // set = value i starts a doc), the fixed-bit dictId stream at bit raw_bit0 of the file. tile_first_doc[t] = start bits

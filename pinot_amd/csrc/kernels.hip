@@ -915,42 +915,104 @@ __device__ __forceinline__ __attribute__((address_space(1))) T* gout(T* p) {
 // found by binary search over the base's packed keys (ascending, compared word nw - 1 first). cnt[b] counts
 // the row (its c is one distinct value of b); pair[i] = b << cbits | c id orders the rows by (group, value).
 // A row without a base group gets b = nbase (it sorts behind every group) and is counted in *miss.
+// the join of both folds: child row i's ids decoded with the child's packing, its g prefix packed as the base packs
+// it, the base group found by binary search; -> the base row, or nbase when the row has none; *cid: the last
+// column's id
+__device__ __forceinline__ int64_t fold_base_row(const uint64_t* __restrict__ ckeys, int64_t i, const DevKeyPack& kc,
+                                                 const DevKeyPack& kb, const uint64_t* __restrict__ bkeys, int64_t nbase,
+                                                 uint64_t* cid) {
+  const int last = kc.ncols - 1;
+  uint64_t kw[kMaxKeyWords];
+  for (int w = 0; w < kb.nw; ++w) kw[w] = 0ull;
+  for (int j = 0; j <= last; ++j) {
+    const int b = 64 - __clzll((unsigned long long)(kc.size[j] - 1) | 1ull);  // bits_for(size): the field's width
+    const uint64_t id = (ckeys[i * kc.nw + kc.word[j]] >> kc.shift[j]) & (b >= 64 ? ~0ull : (1ull << b) - 1ull);
+    if (j == last) *cid = id;
+    else kw[kb.word[j]] |= id << kb.shift[j];
+  }
+  int64_t lo = 0, hi = nbase;  // first base row >= kw
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    int c = 0;
+    for (int w = kb.nw - 1; w >= 0 && c == 0; --w) {
+      const uint64_t x = bkeys[mid * kb.nw + w];
+      c = x < kw[w] ? -1 : x > kw[w] ? 1 : 0;
+    }
+    if (c < 0) lo = mid + 1;
+    else hi = mid;
+  }
+  bool found = lo < nbase;
+  for (int w = 0; w < kb.nw && found; ++w) found = bkeys[lo * kb.nw + w] == kw[w];
+  return found ? lo : nbase;
+}
+
 __global__ void __launch_bounds__(kBlock) distinct_fold_count_kernel(const uint64_t* __restrict__ ckeys, int64_t nrows,
                                                                      DevKeyPack kc, DevKeyPack kb,
                                                                      const uint64_t* __restrict__ bkeys, int64_t nbase,
                                                                      int cbits, uint32_t* cnt, uint64_t* __restrict__ pair,
                                                                      unsigned long long* miss) {
-  const int last = kc.ncols - 1;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nrows; i += (int64_t)gridDim.x * blockDim.x) {
-    uint64_t kw[kMaxKeyWords];
-    for (int w = 0; w < kb.nw; ++w) kw[w] = 0ull;
     uint64_t cid = 0;
-    for (int j = 0; j <= last; ++j) {
-      const int b = 64 - __clzll((unsigned long long)(kc.size[j] - 1) | 1ull);  // bits_for(size): the field's width
-      const uint64_t id = (ckeys[i * kc.nw + kc.word[j]] >> kc.shift[j]) & (b >= 64 ? ~0ull : (1ull << b) - 1ull);
-      if (j == last) cid = id;
-      else kw[kb.word[j]] |= id << kb.shift[j];
-    }
-    int64_t lo = 0, hi = nbase;  // first base row >= kw
-    while (lo < hi) {
-      const int64_t mid = lo + ((hi - lo) >> 1);
-      int c = 0;
-      for (int w = kb.nw - 1; w >= 0 && c == 0; --w) {
-        const uint64_t x = bkeys[mid * kb.nw + w];
-        c = x < kw[w] ? -1 : x > kw[w] ? 1 : 0;
-      }
-      if (c < 0) lo = mid + 1;
-      else hi = mid;
-    }
-    bool found = lo < nbase;
-    for (int w = 0; w < kb.nw && found; ++w) found = bkeys[lo * kb.nw + w] == kw[w];
-    if (found) {
-      atomicAdd(cnt + lo, 1u);  // result unused: a non-returning atomic
-    } else {
-      lo = nbase;
-      atomicAdd(miss, 1ull);
-    }
+    const int64_t lo = fold_base_row(ckeys, i, kc, kb, bkeys, nbase, &cid);
+    if (lo < nbase) atomicAdd(cnt + lo, 1u);  // result unused: a non-returning atomic
+    else atomicAdd(miss, 1ull);
     pair[i] = ((uint64_t)lo << cbits) | cid;
+  }
+}
+
+// DISTINCTCOUNTHLL fold. The register child's rows are (g..., register index) with MAX(rank) in
+// accumulator word `acc_word` of the row's `nacc` exported words, in ACC_MAX's order-preserving double encoding. Per
+// row: the same join, then the rank as one byte at regs[b * m + idx] -- every (group, idx) cell has one row, so a
+// plain store into the zeroed ng x m array. A row without a base group is counted in *miss; an index or rank outside
+// the sketch (no twin produces one) in *bad.
+__global__ void __launch_bounds__(kBlock) hll_fold_place_kernel(const uint64_t* __restrict__ ckeys,
+                                                                const uint64_t* __restrict__ cacc, int nacc, int acc_word,
+                                                                int64_t nrows, DevKeyPack kc, DevKeyPack kb,
+                                                                const uint64_t* __restrict__ bkeys, int64_t nbase,
+                                                                int log2m, uint8_t* __restrict__ regs,
+                                                                unsigned long long* miss, unsigned long long* bad) {
+  const uint64_t m = 1ull << log2m;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nrows; i += (int64_t)gridDim.x * blockDim.x) {
+    uint64_t idx = 0;
+    const int64_t b = fold_base_row(ckeys, i, kc, kb, bkeys, nbase, &idx);
+    if (b >= nbase) {
+      atomicAdd(miss, 1ull);
+      continue;
+    }
+    const double r = decode_ordered_dev(cacc[i * nacc + acc_word], ACC_MAX);
+    if (idx >= m || !(r >= 0.0 && r <= (double)(33 - log2m))) {
+      atomicAdd(bad, 1ull);
+      continue;
+    }
+    regs[(uint64_t)b * m + idx] = (uint8_t)(int)r;
+  }
+}
+
+// HyperLogLog.cardinality()'s inputs, one wave per group: out[2 g] = S = sum over the group's m registers of
+// 2^(32 - reg) (an exact integer: at most 2^16 terms of at most 2^32), out[2 g + 1] = its zero registers. The host
+// forms the estimate (hll.h: no logarithm on the device).
+__global__ void __launch_bounds__(kBlock) hll_estimate_kernel(const uint8_t* __restrict__ regs, int64_t ng, int log2m,
+                                                              unsigned long long* __restrict__ out) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int64_t waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const int64_t m = (int64_t)1 << log2m;
+  for (int64_t g = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; g < ng; g += waves) {
+    unsigned long long s = 0, z = 0;
+    const uint8_t* R = regs + g * m;
+    for (int64_t j = lane; j < m; j += 64) {
+      const uint32_t r = R[j];
+      s += 1ull << (32 - (r > 32u ? 32u : r));
+      z += r == 0u;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      s += __shfl_down(s, o, 64);
+      z += __shfl_down(z, o, 64);
+    }
+    if (lane == 0) {
+      out[2 * g] = s;
+      out[2 * g + 1] = z;
+    }
   }
 }
 
@@ -2441,6 +2503,26 @@ hipError_t launch_distinct_fold_count(const uint64_t* ckeys, int64_t nrows, cons
   if (e != hipSuccess || nrows <= 0) return e;
   hipLaunchKernelGGL(distinct_fold_count_kernel, dim3(grid_cap(nrows, kBlock, 8192)), dim3(kBlock), 0, st, ckeys, nrows, kc,
                      kb, bkeys, nbase, cbits, cnt, pair, miss);
+  return hipGetLastError();
+}
+
+// regs: ng << log2m bytes, zeroed here; sz: 2 ng words (S, zeros per group); miss / bad: one word each, zeroed here.
+// ckeys / cacc: the register child's nrows exported rows (nacc accumulator words each)
+hipError_t launch_hll_fold(const uint64_t* ckeys, const uint64_t* cacc, int nacc, int acc_word, int64_t nrows,
+                           const DevKeyPack& kc, const DevKeyPack& kb, const uint64_t* bkeys, int64_t nbase, int log2m,
+                           uint8_t* regs, unsigned long long* sz, unsigned long long* miss, unsigned long long* bad,
+                           hipStream_t st) {
+  if (log2m < 4 || log2m > 16 || nbase < 0 || nbase >= ((int64_t)1 << (31 - log2m))) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(miss, 0, 8, st);
+  if (e == hipSuccess) e = hipMemsetAsync(bad, 0, 8, st);
+  if (e == hipSuccess && nbase > 0) e = hipMemsetAsync(regs, 0, (size_t)nbase << log2m, st);
+  if (e != hipSuccess) return e;
+  if (nrows > 0)
+    hipLaunchKernelGGL(hll_fold_place_kernel, dim3(grid_cap(nrows, kBlock, 8192)), dim3(kBlock), 0, st, ckeys, cacc, nacc,
+                       acc_word, nrows, kc, kb, bkeys, nbase, log2m, regs, miss, bad);
+  if (nbase > 0)
+    hipLaunchKernelGGL(hll_estimate_kernel, dim3(grid_cap(nbase * 64, kBlock, 8192)), dim3(kBlock), 0, st, regs, nbase,
+                       log2m, sz);
   return hipGetLastError();
 }
 

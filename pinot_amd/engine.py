@@ -37,7 +37,7 @@ TYPE_CODE = {INT: 0, LONG: 1, FLOAT: 2, DOUBLE: 3, STRING: 4}
 ENC_CODE = {"FIXED_BIT": 0, "RAW": 1, "SORTED": 2, "FIXED_BIT_MV": 3}
 PRED_CODE = {"EQ": 0, "NOT_EQ": 1, "IN": 2, "NOT_IN": 3, "RANGE": 4, "REGEXP_LIKE": 5}  # (6: REGEXP_LIKE, 'i')
 AGG_CODE = {"COUNT": 0, "SUM": 1, "MIN": 2, "MAX": 3, "SUMLONG": 4, "AVG": 5, "MINMAXRANGE": 6,
-            "DISTINCTCOUNT": 7, "PERCENTILE": 8, "DISTINCTSUM": 9, "DISTINCTAVG": 10,
+            "DISTINCTCOUNT": 7, "PERCENTILE": 8, "DISTINCTSUM": 9, "DISTINCTAVG": 10, "DISTINCTCOUNTHLL": 17,
             "COUNTMV": 11, "SUMMV": 12, "MINMV": 13, "MAXMV": 14, "AVGMV": 15, "MINMAXRANGEMV": 16}
 EXPR_CODE = {"MUL": 1, "SUB": 2, "ADD": 3}
 
@@ -280,8 +280,9 @@ class DistinctCountResult:
     (query.split_distinct_count): the base result plus one grouped result per such column, folded into per-group
     value sets and histograms."""
 
-    def __init__(self, qc, base, subs, server_trim: bool = False):
+    def __init__(self, qc, base, subs, server_trim: bool = False, column_types=None):
         self.qc, self._base, self._subs = qc, base, subs
+        self._column_types = column_types  # column -> stored type (DISTINCTCOUNTHLL hashes by it)
         self._server_trim = server_trim  # the server's combine table over the folded groups
 
     def num_docs_matched(self) -> int:
@@ -297,7 +298,8 @@ class DistinctCountResult:
         return [self._base] + [r for _, r in self._subs]
 
     def groups(self):
-        g = fold_distinct_count(self.qc, self._base.groups(), [(i, r.groups()) for i, r in self._subs])
+        g = fold_distinct_count(self.qc, self._base.groups(), [(i, r.groups()) for i, r in self._subs],
+                                self._column_types)
         return server_table(self.qc, g) if self._server_trim else g
 
     def rows(self):
@@ -507,6 +509,21 @@ class QueryResult:
                        for i in np.unique(vals)}
         return sets_from_csr(off, vals, stored_type, strings)
 
+    def hll_registers(self, native_idx: int, num_groups: int) -> List[tuple]:
+        """The sketches of library aggregation `native_idx` (a DISTINCTCOUNTHLL), one (log2m, registers bytes) per
+        group in fetch order (pinot_amd_result_fetch_hll)."""
+        L = lib()
+        log2m, ng = C.c_int32(), C.c_int64()
+        check(L.pinot_amd_result_fetch_hll(self._h, native_idx, 0, None, C.byref(log2m), C.byref(ng)), "fetch_hll")
+        m = 1 << log2m.value
+        buf = np.zeros(max(ng.value * m, 1), dtype=np.uint8)
+        check(L.pinot_amd_result_fetch_hll(self._h, native_idx, buf.size, buf.ctypes.data, C.byref(log2m), C.byref(ng)),
+              "fetch_hll")
+        if ng.value != num_groups:
+            raise _lib.PinotAmdError(f"fetch_hll: {ng.value} groups, fetch returned {num_groups}")
+        raw = buf.tobytes()
+        return [(log2m.value, raw[g * m:(g + 1) * m]) for g in range(num_groups)]
+
     def value_hists(self, native_idx: int, stored_type: str, num_groups: int) -> List[dict]:
         """The histograms of library aggregation `native_idx` (a PERCENTILE), one dict distinct_value -> matching
         docs per group in fetch order (pinot_amd_result_fetch_value_counts -> query.hists_from_csr)."""
@@ -561,6 +578,11 @@ class QueryResult:
                     acols.append([DistinctSize(c) for c in vi[:, slot[1]].tolist()])
                 else:
                     acols.append(self.distinct_sets(slot[1], slot[2], n))
+            elif slot[0] == "hll":  # DISTINCTCOUNTHLL executed by the library: the estimate, or the registers
+                if distinct_sizes:
+                    acols.append([FinalValue(x) for x in vi[:, slot[1]].tolist()])
+                else:
+                    acols.append(self.hll_registers(slot[1], n))
             elif slot[0] in ("hist", "dset"):  # PERCENTILE / DISTINCTSUM / DISTINCTAVG executed by the library
                 if distinct_sizes:
                     acols.append([FinalValue(x) for x in v[:, slot[1]].tolist()])
@@ -809,7 +831,10 @@ class ServerQueryExecutor:
             base, subs = split_distinct_count(qc)
             return DistinctCountResult(qc, self._execute(base, segments, stream, key_space, server_trim=False),
                                        [(i, self._execute(sq, segments, stream, key_space, server_trim=False))
-                                        for i, sq in subs], server_trim=trim)
+                                        for i, sq in subs], server_trim=trim,
+                                       column_types={a.column: segments[0].columns[a.column].stored_type
+                                                     for a in qc.aggregations
+                                                     if a.func == "DISTINCTCOUNTHLL" and a.column in segments[0].columns})
         return self._execute(qc, segments, stream, key_space)
 
     def _execute_selection(self, qc: QueryContext, segments: Sequence[ImmutableSegment], stream=None) -> SelectionResult:
@@ -907,7 +932,10 @@ class ServerQueryExecutor:
                     return native.index(key)
                 idx = C.c_int32()
                 abi_col = column.encode() if (expr is not None or column == "*") else names.abi(column)
-                if func in MV_FUNCS:  # the multi-value functions' entry point
+                if func == "DISTINCTCOUNTHLL":  # its own entry point: the literal is log2m
+                    check(L.pinot_amd_query_add_aggregation_hll(qh, abi_col, int(param), C.byref(idx)),
+                          f"add_aggregation_hll({column})")
+                elif func in MV_FUNCS:  # the multi-value functions' entry point
                     check(L.pinot_amd_query_add_aggregation_mv(qh, AGG_CODE[func], column.encode(), C.byref(idx)),
                           f"add_aggregation_mv({func})")
                 elif AGG_CODE[func] > AGG_CODE["DISTINCTCOUNT"]:  # the functions with a literal argument's entry point
@@ -942,6 +970,10 @@ class ServerQueryExecutor:
                     if col is None:
                         raise _lib.PinotAmdError(f"unknown column {a.column!r} in segment {first.name}")
                     agg_slots.append(("distinct", add("DISTINCTCOUNT", a.column, None, None, a.filter), col.stored_type))
+                elif a.func == "DISTINCTCOUNTHLL":  # the library builds and folds the registers
+                    if names.column(a.column) is None:
+                        raise _lib.PinotAmdError(f"unknown column {a.column!r} in segment {first.name}")
+                    agg_slots.append(("hll", add(a.func, a.column, None, a.param, a.filter)))
                 elif a.func in VALUE_SET_FUNCS:    # PERCENTILE / DISTINCTSUM / DISTINCTAVG, likewise
                     col = names.column(a.column)
                     if col is None:

@@ -20,14 +20,21 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 AGG_FUNCS = ("COUNT", "SUM", "MIN", "MAX", "AVG", "SUMLONG", "MINMAXRANGE", "DISTINCTCOUNT", "PERCENTILE",
-             "DISTINCTSUM", "DISTINCTAVG", "COUNTMV", "SUMMV", "MINMV", "MAXMV", "AVGMV", "MINMAXRANGEMV")
+             "DISTINCTSUM", "DISTINCTAVG", "COUNTMV", "SUMMV", "MINMV", "MAXMV", "AVGMV", "MINMAXRANGEMV",
+             "DISTINCTCOUNTHLL")
 # the aggregations over a multi-value column: every value of a matching doc counts (CountMV / SumMV / MinMV / MaxMV /
 # AvgMV / MinMaxRangeMVAggregationFunction); partials as their SV parents': AVGMV (sum, count of values),
 # MINMAXRANGEMV (min, max)
 MV_FUNCS = ("COUNTMV", "SUMMV", "MINMV", "MAXMV", "AVGMV", "MINMAXRANGEMV")
 # the aggregations answered from a (group-by columns..., column) COUNT(*) query: each group's histogram over the
 # column's distinct values (split_distinct_count)
-VALUE_SET_FUNCS = ("DISTINCTCOUNT", "PERCENTILE", "DISTINCTSUM", "DISTINCTAVG")
+VALUE_SET_FUNCS = ("DISTINCTCOUNT", "PERCENTILE", "DISTINCTSUM", "DISTINCTAVG", "DISTINCTCOUNTHLL")
+# DistinctCountHLLAggregationFunction: log2m of DISTINCTCOUNTHLL(c) (CommonConstants.Helix.DEFAULT_HYPERLOGLOG_LOG2M)
+# and the range the engine takes
+HLL_DEFAULT_LOG2M, HLL_MIN_LOG2M, HLL_MAX_LOG2M = 8, 4, 16
+# the sketch functions the engine refuses by name (canonical: upper case, no underscores)
+HLL_REFUSED_FUNCS = ("DISTINCTCOUNTRAWHLL", "DISTINCTCOUNTHLLPLUS", "DISTINCTCOUNTRAWHLLPLUS", "DISTINCTCOUNTSMARTHLL",
+                     "DISTINCTCOUNTHLLMV", "DISTINCTCOUNTRAWHLLMV", "DISTINCTCOUNTHLLPLUSMV")
 DEFAULT_GROUP_BY_LIMIT = 10          # Pinot's default LIMIT for group-by results
 DEFAULT_NUM_GROUPS_LIMIT = 100_000   # InstancePlanMakerImplV2.DEFAULT_NUM_GROUPS_LIMIT
 
@@ -217,6 +224,15 @@ def check_percentile(p) -> float:
     return p
 
 
+def check_log2m(v) -> int:
+    """DISTINCTCOUNTHLL's second argument: an integer, 4 <= log2m <= 16 here."""
+    if isinstance(v, str) and v.strip().lstrip("+").isdigit():
+        v = int(v)
+    if isinstance(v, bool) or not isinstance(v, int) or not HLL_MIN_LOG2M <= v <= HLL_MAX_LOG2M:
+        raise ValueError(f"DISTINCTCOUNTHLL: log2m {v!r} is not an integer in [{HLL_MIN_LOG2M}, {HLL_MAX_LOG2M}]")
+    return v
+
+
 def agg_head(word: str):
     """(function, percentile or None) when `word` names an aggregation function -- PERCENTILE with up to three
     digits after the name carries its percentile (AggregationFunctionFactory.java:143,191) -- else None."""
@@ -225,6 +241,11 @@ def agg_head(word: str):
         return w, None
     if w.replace("_", "") in MV_FUNCS:  # Pinot canonicalises function names: SUM_MV is SUMMV
         return w.replace("_", ""), None
+    if w.replace("_", "") == "DISTINCTCOUNTHLL":  # distinct_count_hll
+        return "DISTINCTCOUNTHLL", None
+    if w.replace("_", "") in HLL_REFUSED_FUNCS:
+        raise ValueError(f"{word} is not supported: of the sketch functions only DISTINCTCOUNTHLL over a single-value "
+                         "column (raw / HLL++ / smart sketches and multi-value columns are not)")
     m = _PERCENTILE_N.match(w)
     if m:
         return "PERCENTILE", check_percentile(m.group(1))
@@ -870,6 +891,8 @@ class _Parser:
                 else:
                     col, expr = self.agg_arg(func)
                 param = self.percentile_arg(func, param)
+                if func == "DISTINCTCOUNTHLL" and (col == "*" or expr is not None or expression(col) is not None):
+                    raise ValueError(f"DISTINCTCOUNTHLL({col}) is not supported: it takes one column, not an expression")
                 self.eat_op(")")
                 agg_filter = self.agg_filter()
                 alias = None
@@ -958,6 +981,12 @@ class _Parser:
     def percentile_arg(self, func, param):
         """PERCENTILE(c, 50) / PERCENTILE(c, 99.9) / PERCENTILE(c, '50'): the second argument, unless the
         function's name carried the percentile."""
+        if func == "DISTINCTCOUNTHLL":  # DISTINCTCOUNTHLL(c [, log2m]): an integer literal
+            log2m = HLL_DEFAULT_LOG2M
+            if self.peek() == ("op", ","):
+                self.i += 1
+                log2m = self.literal()
+            return check_log2m(log2m)
         if func != "PERCENTILE":
             return None
         if self.peek() == ("op", ","):
@@ -1220,6 +1249,8 @@ def final_value(func: str, partial, param=None):
         return mx - mn
     if func == "DISTINCTCOUNT":
         return len(partial)
+    if func == "DISTINCTCOUNTHLL":  # partial: (log2m, registers), or the library's estimate
+        return int(partial.v) if isinstance(partial, FinalValue) else hll_cardinality(partial[1])
     if func not in _HISTOGRAM_FINALS:  # (one look-up on the path of the plain aggregations)
         return partial
     if isinstance(partial, FinalValue):
@@ -1249,6 +1280,8 @@ def merge_partial(func: str, a, b):
         return (min(a[0], b[0]), max(a[1], b[1]))
     if func in ("DISTINCTCOUNT", "DISTINCTSUM", "DISTINCTAVG"):
         return a | b
+    if func == "DISTINCTCOUNTHLL":
+        return hll_merge(a, b)
     if func == "PERCENTILE":  # histograms (distinct_value -> matching docs) add
         out = dict(a)
         for v, c in b.items():
@@ -1326,10 +1359,13 @@ def canonical_key(key) -> tuple:
     return tuple(distinct_value(v) for v in key)
 
 
-def fold_distinct_count(qc: QueryContext, base_groups: dict, sub_groups: Sequence[Tuple[int, dict]]) -> dict:
+def fold_distinct_count(qc: QueryContext, base_groups: dict, sub_groups: Sequence[Tuple[int, dict]],
+                        column_types: Optional[Dict[str, str]] = None) -> dict:
     """Groups of the original query from split_distinct_count's results (same group keys as the
     base query: a group exists iff a doc matched, in every one of the queries alike). Keys and set
-    elements are matched by distinct_value (bit patterns for floats), never by Python float equality."""
+    elements are matched by distinct_value (bit patterns for floats), never by Python float equality.
+    column_types: column -> stored type, which DISTINCTCOUNTHLL's hash depends on (without it: LONG for Python ints,
+    DOUBLE for floats, STRING for strings); its partial is (log2m, registers) hashed here from the distinct values."""
     # per sub query: group -> value set, or -- when a PERCENTILE reads the column -- group -> histogram
     # (distinct_value -> matching docs: the sub query's COUNT(*))
     by_column = {qc.aggregations[i].column: i for i, _ in sub_groups}
@@ -1354,9 +1390,124 @@ def fold_distinct_count(qc: QueryContext, base_groups: dict, sub_groups: Sequenc
         for j, a in enumerate(qc.aggregations):
             if a.func in VALUE_SET_FUNCS:
                 h = hists[by_column[a.column]].get(ck, {})
-                full[j] = dict(h) if a.func == "PERCENTILE" else frozenset(h)
+                if a.func == "DISTINCTCOUNTHLL":
+                    t = (column_types or {}).get(a.column)
+                    full[j] = (int(a.param), hll_registers(h, t, int(a.param)))
+                else:
+                    full[j] = dict(h) if a.func == "PERCENTILE" else frozenset(h)
         out[key] = full
     return out
+
+
+# ----------------------------------------------------------------------------- DISTINCTCOUNTHLL
+# DistinctCountHLLAggregationFunction over stream-lib's HyperLogLog and MurmurHash, restated (the library's
+# restatement is csrc/hll.h). All hash arithmetic is Java int: 32 bits, wrapping, >>> logical.
+_M32 = 0xFFFFFFFF
+_MURMUR_M = 0x5BD1E995
+
+
+def _hash_long(d: int) -> int:
+    """MurmurHash.hashLong(long)."""
+    m = _MURMUR_M
+    k = ((d & _M32) * m) & _M32
+    k ^= k >> 24
+    h = (k * m) & _M32
+    k = (((d >> 32) & _M32) * m) & _M32
+    k ^= k >> 24
+    h = (h * m) & _M32
+    h ^= (k * m) & _M32
+    h ^= h >> 13
+    h = (h * m) & _M32
+    h ^= h >> 15
+    return h
+
+
+def _hash_bytes(data: bytes, seed: int = -1) -> int:
+    """MurmurHash.hash(byte[], length, seed): MurmurHash2 with its tail bytes sign-extended (Java bytes)."""
+    m = _MURMUR_M
+    n = len(data)
+    h = (seed ^ n) & _M32
+    for i in range(0, n - (n & 3), 4):
+        k = int.from_bytes(data[i:i + 4], "little")
+        k = (k * m) & _M32
+        k ^= k >> 24
+        k = (k * m) & _M32
+        h = (h * m) & _M32
+        h ^= k
+    left = n & 3
+    if left:
+        sb = [b - 256 if b >= 128 else b for b in data[n - left:]]
+        if left >= 3:
+            h ^= (sb[-3] << 16) & _M32
+        if left >= 2:
+            h ^= (sb[-2] << 8) & _M32
+        h ^= sb[-1] & _M32
+        h = (h * m) & _M32
+    h ^= h >> 13
+    h = (h * m) & _M32
+    h ^= h >> 15
+    return h
+
+
+def hll_hash(value, stored_type: Optional[str] = None) -> int:
+    """MurmurHash.hash(Object) of a column value boxed as its stored type, as an unsigned 32-bit int: INT / LONG
+    hashLong(v); FLOAT hashLong((long) floatToRawIntBits); DOUBLE hashLong(doubleToRawLongBits); STRING the UTF-8
+    bytes up to the first NUL with seed -1. `value` may be a distinct_value identity (("f", bits) for floats)."""
+    if isinstance(value, tuple):  # distinct_value of a float: the double's bits
+        value = struct.unpack("<d", struct.pack("<q", value[1]))[0]
+    if stored_type is None:
+        stored_type = "STRING" if isinstance(value, str) else "DOUBLE" if isinstance(value, (float, np.floating)) else "LONG"
+    if stored_type == "STRING":
+        return _hash_bytes(str(value).encode("utf-8").split(b"\0", 1)[0])
+    if stored_type == "FLOAT":
+        return _hash_long(struct.unpack("<i", struct.pack("<f", float(value)))[0])
+    if stored_type == "DOUBLE":
+        return _hash_long(struct.unpack("<q", struct.pack("<d", float(value)))[0])
+    return _hash_long(int(value))
+
+
+def hll_registers(values, stored_type: Optional[str], log2m: int) -> bytes:
+    """The RegisterSet of a HyperLogLog(log2m) offered `values` (HyperLogLog.offerHashed), one byte per register."""
+    log2m = check_log2m(log2m)
+    regs = bytearray(1 << log2m)
+    tail = (1 << (log2m - 1)) + 1
+    for v in values:
+        x = hll_hash(v, stored_type)
+        j = x >> (32 - log2m)
+        w = ((x << log2m) & _M32) | tail
+        r = 32 - w.bit_length() + 1  # Integer.numberOfLeadingZeros(w) + 1
+        if r > regs[j]:
+            regs[j] = r
+    return bytes(regs)
+
+
+def hll_merge(a, b):
+    """HyperLogLog.addAll: the element-wise maximum of two (log2m, registers) partials of equal log2m."""
+    if a[0] != b[0] or len(a[1]) != len(b[1]):
+        raise ValueError(f"cannot merge HyperLogLogs of log2m {a[0]} and {b[0]}")
+    return (a[0], bytes(map(max, a[1], b[1])))
+
+
+JAVA_LONG_MAX = (1 << 63) - 1
+
+
+def hll_cardinality(registers) -> int:
+    """HyperLogLog.cardinality() of a register array (2^log2m bytes): the one estimator both Python paths use.
+    Math.round(+inf) = Long.MAX_VALUE when the small-range correction meets no zero register."""
+    regs = bytes(registers)
+    m = len(regs)
+    log2m = m.bit_length() - 1
+    if m != 1 << log2m or not HLL_MIN_LOG2M <= log2m <= HLL_MAX_LOG2M:
+        raise ValueError(f"{m} registers are not a HyperLogLog of log2m {HLL_MIN_LOG2M}..{HLL_MAX_LOG2M}")
+    s = sum(1 << (32 - r) for r in regs) / 4294967296.0  # exact: every term a multiple of 2^-25, the total <= 2^16
+    zeros = regs.count(0)
+    alpha_mm = {4: 0.673, 5: 0.697, 6: 0.709}.get(log2m, 0.7213 / (1 + 1.079 / m)) * m * m
+    estimate = alpha_mm * (1 / s)
+    if estimate <= 2.5 * m:
+        if zeros == 0:
+            return JAVA_LONG_MAX
+        return int(math.floor(m * math.log(m / float(zeros)) + 0.5))
+    return int(math.floor(estimate + 0.5))
 
 
 def _value_as_double(v) -> float:
