@@ -525,6 +525,62 @@ int pinot_amd_query_add_selection_order_by(pinot_amd_query* q, const char* colum
 int pinot_amd_query_set_selection_limit(pinot_amd_query* q, int64_t limit, int64_t offset);
 
 /* ------------------------------------------------------------------------------------------------
+ * Distinct queries: SELECT DISTINCT a, b FROM t WHERE ... [ORDER BY a DESC, ...] LIMIT n
+ * (core/plan/DistinctPlanNode.java -> core/operator/query/DistinctOperator.java /
+ * DictionaryBasedDistinctOperator.java per segment -> core/operator/combine/DistinctCombineOperator.java, with
+ * core/query/distinct/DistinctExecutorFactory.java and core/query/distinct/table/MultiColumnDistinctTable.java).
+ * pinot_amd_query_set_distinct turns a query into a distinct query: its distinct columns are the keys added with
+ * pinot_amd_query_add_group_by / _add_group_by_transform, in order; its ORDER BY the pinot_amd_query_add_order_by
+ * entries of kind 0; `limit` its LIMIT (Pinot's default is 10). The scan records one presence bit per matching
+ * doc -- no accumulator, no COUNT cell -- in a bitmap indexed by the row's rank in the result order, so the answer
+ * is the bitmap's first LIMIT set bits.
+ *   - Columns: single-value columns of any stored type, dictionary, sorted or raw, an expression
+ *     (pinot_amd_query_define_expression) or a time-bucket transform, exactly as GROUP BY keys. Values are
+ *     identified as group keys are (FLOAT / DOUBLE by floatToIntBits / doubleToLongBits: one NaN, -0.0 != 0.0).
+ *     A multi-value column is EUNSUPPORTED (DistinctExecutorFactory's processMV is not restated).
+ *   - Result: the distinct rows over every doc matching the filter in every segment of the batch, cut to LIMIT.
+ *   - With ORDER BY (only distinct columns can be named: Pinot asserts it) the first LIMIT rows in that order.
+ *     Values compare as the server table compares group columns (numerically, Double.compare, String.compareTo;
+ *     DESC reverses). Rows equal on the ORDER BY columns are ordered by ascending global group key; Pinot leaves
+ *     such ties to a hash set's iteration order, so this is one of its possible answers.
+ *   - Without ORDER BY Pinot keeps whichever LIMIT rows it meets first and stops scanning
+ *     (DistinctTable.addWithoutOrderBy returns true, DistinctOperator breaks). Here the segments are scanned in
+ *     batch order in groups of 1, 2, 4, ... segments (as a selection without ORDER BY); the scan stops after the
+ *     first group that leaves at least LIMIT distinct rows held, or after the last segment, and the result is the
+ *     first LIMIT held rows in ascending global key order. A hash plan scans the whole batch.
+ *   - LIMIT 0: no row, a valid schema, nothing scanned. numGroupsLimit does not apply (a DistinctTable knows
+ *     only its limit).
+ *   - One dictionary-encoded or sorted column and no filter (DictionaryBasedDistinctOperator): the first LIMIT
+ *     values of the batch's merged dictionary, the last LIMIT with ORDER BY ... DESC; no kernel runs;
+ *     num_docs_matched is the sum over the segments of min(LIMIT, cardinality), as that operator reports.
+ *   - Plans: key spaces up to 2^31 keys take the bitmap -- in a 256-thread block's LDS up to 327 680 keys, in one
+ *     CU-wide block's LDS up to about 1.3 M keys (LDS bitmaps are OR-ed into the HBM bitmap once per block), in HBM
+ *     above that; larger key spaces, or PINOT_AMD_GROUP_PLAN=hash, take the COUNT-only hash plan, whose groups are
+ *     cut to LIMIT by the ordered table. PINOT_AMD_DISTINCT_PLAN=lds|wide|hbm|hash pins the kind (tests).
+ * pinot_amd_execute fails with EINVAL for a distinct query without a key, with an aggregation, a selection
+ * column, an ORDER BY of kind 1, or with pinot_amd_query_set_result_limit / _set_server_options /
+ * _set_segment_trim called on it; with EUNSUPPORTED, naming the column, for a multi-value key and for
+ * pinot_amd_query_set_group_key_values (there is no multi-GPU merge of distinct results).
+ * pinot_amd_execute_filter ignores the distinct flag and limit; both are part of a prepared plan's identity.
+ *
+ * The result calls on a distinct result:
+ *   pinot_amd_result_num_groups         the rows held, at most LIMIT
+ *   pinot_amd_result_fetch              the rows' values as a GROUP BY fetch returns keys, in result order;
+ *                                       h_values / h_values_i64 may be NULL (there are no aggregations)
+ *   pinot_amd_result_string_key         as for a group-by result
+ *   pinot_amd_result_num_docs_matched   the docs matching the filter in the segments actually scanned
+ *   pinot_amd_execute_again             re-zeroes the bitmap and re-runs every pass; last_kernel_ms covers them
+ *   kernel_info                         "jit-distinct-lds", "jit-distinct-wide", "jit-distinct-hbm" (" xN" for N
+ *                                       launches run, when N != 1), the hash plan's name, or "distinct-dictionary"
+ *   algorithmic_bytes                   the filter and distinct columns of the scanned segments, streamed once
+ *   check_word                          reads 0
+ *   fetch_intermediate, fetch_distinct_values, fetch_value_counts: EINVAL
+ *   accumulators, export_groups, merge_groups: EUNSUPPORTED
+ * --------------------------------------------------------------------------------------------- */
+/* limit >= 0 (EINVAL otherwise). */
+int pinot_amd_query_set_distinct(pinot_amd_query* q, int64_t limit);
+
+/* ------------------------------------------------------------------------------------------------
  * Execution and results (IntermediateResultsBlock / AggregationGroupByResult equivalents).
  * --------------------------------------------------------------------------------------------- */
 typedef struct pinot_amd_result pinot_amd_result;

@@ -144,6 +144,7 @@ SIGNATURES = {
     "pinot_amd_query_add_selection": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int32)]),
     "pinot_amd_query_add_selection_order_by": (C.c_int, [_P, C.c_char_p, C.c_int32]),
     "pinot_amd_query_set_selection_limit": (C.c_int, [_P, C.c_int64, C.c_int64]),
+    "pinot_amd_query_set_distinct": (C.c_int, [_P, C.c_int64]),
     "pinot_amd_result_selection_num_columns": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "pinot_amd_result_selection_column": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
     "pinot_amd_result_num_rows": (C.c_int, [_P, _I64P]),

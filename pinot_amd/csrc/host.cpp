@@ -68,6 +68,8 @@ static const std::set<std::string>& kept_knobs() {
       "PINOT_AMD_ADMIT_PREFIX",
       "PINOT_AMD_ADMIT_SEQ",
       "PINOT_AMD_ATOMIC_HANDOVER",
+      "PINOT_AMD_DISTINCT_LDS_READ",
+      "PINOT_AMD_DISTINCT_PLAN",
       "PINOT_AMD_FILTER_GATE",
       "PINOT_AMD_FLUSH_EVERY",
       "PINOT_AMD_FLUSH_GROUP",
@@ -1655,6 +1657,12 @@ struct pinot_amd_query {
   // than aggs, or an empty entry: the main filter alone); skip_empty_groups: filteredAggregationsSkipEmptyGroups
   std::vector<std::vector<PredSpec>> agg_filter;
   int skip_empty_groups = 0;
+  // SELECT DISTINCT (pinot_amd_query_set_distinct, DistinctPlanNode): the group_by keys are the distinct columns,
+  // order_by (kind 0 only) the ORDER BY, distinct_limit the LIMIT. The group-by result options have no meaning on it:
+  // which of their setters were called is kept so that pinot_amd_execute can refuse the combination
+  bool distinct = false;
+  int64_t distinct_limit = 10;
+  bool set_result_limit = false, set_server_options = false, set_segment_trim = false;
   const std::vector<PredSpec>* filter_of(size_t ai) const {
     return ai < agg_filter.size() && !agg_filter[ai].empty() ? &agg_filter[ai] : nullptr;
   }
@@ -1961,6 +1969,7 @@ int pinot_amd_query_set_result_limit(pinot_amd_query* q, int64_t limit, int64_t 
   q->limit = limit;
   q->min_trim = min_server_group_trim_size;
   q->trim_threshold = group_trim_threshold;
+  q->set_result_limit = true;
   return 0;
 }
 
@@ -1969,12 +1978,21 @@ int pinot_amd_query_set_server_options(pinot_amd_query* q, int32_t server_return
   if (!q || sort_aggregate_limit_threshold <= 0) return fail(PINOT_AMD_EINVAL, "set_server_options: bad arguments");
   q->server_final = server_return_final_result ? 1 : 0;
   q->sort_agg_threshold = sort_aggregate_limit_threshold;
+  q->set_server_options = true;
   return 0;
 }
 
 int pinot_amd_query_set_segment_trim(pinot_amd_query* q, int64_t min_segment_group_trim_size) {
   if (!q) return fail(PINOT_AMD_EINVAL, "set_segment_trim: null query");
   q->min_seg_trim = min_segment_group_trim_size;
+  q->set_segment_trim = true;
+  return 0;
+}
+
+int pinot_amd_query_set_distinct(pinot_amd_query* q, int64_t limit) {
+  if (!q || limit < 0) return fail(PINOT_AMD_EINVAL, "set_distinct: bad arguments");
+  q->distinct = true;
+  q->distinct_limit = limit;
   return 0;
 }
 
@@ -2301,6 +2319,21 @@ struct pinot_amd_result {
   std::vector<int32_t> row_seg, row_doc;
   std::vector<int64_t> row_vals;                        // sel_nrows x sel_nout (fetch's key encoding)
   std::vector<std::vector<std::string>> row_strings;    // per selected STRING column: the kept rows' strings by id
+  // SELECT DISTINCT (run_distinct, compact_distinct). dist_kind: the presence-bitmap plan's table kind
+  // (JitPlan::DISTINCT_*), 0 for a hash plan (the ordinary COUNT-only hash plan, its groups cut to LIMIT by the
+  // ordered table path) and for the dictionary-only answer (dist_dict: one dictionary column, no filter -- the
+  // merged dictionary's first / last LIMIT values, no kernel). The bitmap plans index dist_bits (num_keys bits) by
+  // the row's rank in the result order (dist_ord, JitPlan::dist_ord); without ORDER BY the launches run in the
+  // selection's groups (sel_ngroups / sel_groups_run) until LIMIT bits are held.
+  bool distinct = false, dist_dict = false;
+  int dist_kind = 0;
+  int64_t dist_limit = 10;
+  std::vector<JitPlan::OrdCol> dist_ord;
+  DevBuf dist_bits;
+  int64_t dist_dict_matched = 0;  // the dictionary-only answer's numDocsScanned: sum of min(LIMIT, cardinality)
+  bool dist_bitmap() const { return distinct && !dist_dict && dist_kind != 0; }
+  // answered by run_distinct / compact_distinct instead of the group-by path
+  bool dist_own() const { return distinct && (dist_dict || dist_kind != 0 || dist_limit == 0); }
   ~pinot_amd_result() {
     expr_twin_pin(this, false);
     if (ev0) (void)hipEventDestroy(ev0);
@@ -2417,6 +2450,10 @@ static std::string plan_identity(const pinot_amd_query& Q, const std::vector<pin
     k += "|";
     num(Q.sel_limit);
     num(Q.sel_offset);
+    if (Q.distinct) {  // (pinot_amd_execute_filter ignores the distinct flag and limit too)
+      k += "|DQ";
+      num(Q.distinct_limit);
+    }
   }
   k += "|S";
   for (auto* sg : segs) k += std::to_string(sg->uid) + "." + std::to_string(sg->gen) + ",";
@@ -4059,7 +4096,53 @@ static int run_selection(pinot_amd_result* r) {
   return 0;
 }
 
+// SELECT DISTINCT on a presence bitmap (DistinctOperator over a DistinctTable, restated on the dense key space):
+// every launch ORs its matching docs' rows into the one bitmap, indexed by the rows' rank in the result order, so
+// the answer is the bitmap's first LIMIT set bits (compact_distinct). With an ORDER BY every segment is scanned.
+// Without one Pinot keeps the LIMIT rows it meets first and stops (DistinctOperator breaks once
+// DistinctTable.addWithoutOrderBy reports the limit); here the segments launch in batch order in groups of 1, 2,
+// 4, ... (as run_selection's) and the scan stops after the first group that leaves at least LIMIT bits set.
+// LIMIT 0 and the dictionary-only answer run nothing.
+static int run_distinct(pinot_amd_result* r) {
+  hipStream_t st = r->stream;
+  r->compacted = false;
+  r->merged = false;
+  r->check_failed = false;
+  r->sel_groups_run = 0;
+  HIP_OK(hipEventRecord(r->ev0, st));
+  HIP_OK(hipMemsetAsync(r->matched.p, 0, r->matched.n, st));
+  if (r->dist_limit == 0 || r->dist_dict) {
+    HIP_OK(hipEventRecord(r->ev1, st));
+    return 0;
+  }
+  if (int rc = run_mv_leaves(r, st)) return rc;
+  if (!r->inv_leaves.empty())
+    HIP_OK(launch_expand_jobs(r->d_expand_jobs.p, (int32_t)r->inv_leaves.size(), r->expand_total, st));
+  HIP_OK(hipMemsetAsync(r->dist_bits.p, 0, r->dist_bits.n, st));
+  const size_t nl = r->launches.size();
+  DevHash H{};
+  for (int g = 0; g < r->sel_ngroups; ++g) {
+    for (size_t li = 0; li < nl; ++li)
+      if (r->launches[li].batch == g)
+        if (int rc = launch_one(r, r->launches[li], li, (uint64_t*)r->dist_bits.p, H)) return rc;
+    ++r->sel_groups_run;
+    if (!r->srv_order.empty() || g + 1 == r->sel_ngroups) continue;
+    // between the groups: the rows held so far (the set bits), read back as run_selection reads its count
+    if (int rc = r->c_counts.ensure((size_t)compact_num_chunks(r->q.num_keys) * 8)) return rc;
+    if (int rc = r->c_total.ensure(8)) return rc;
+    HIP_OK(launch_bitset_count((const uint64_t*)r->dist_bits.p, r->q.num_keys, (int64_t*)r->c_counts.p,
+                               (int64_t*)r->c_total.p, st));
+    int64_t held = 0;
+    HIP_OK(hipMemcpyAsync(&held, r->c_total.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (held >= r->dist_limit) break;
+  }
+  HIP_OK(hipEventRecord(r->ev1, st));
+  return 0;
+}
+
 static int run_plan(pinot_amd_result* r) {
+  if (r->dist_own()) return run_distinct(r);
   if (r->topk) {
     try {  // (execute_again reaches this outside the ABI's exception guard)
       return run_selection(r);
@@ -4392,6 +4475,8 @@ struct PlanBuild {
   void* stream = nullptr;
   bool filter_only = false;
   bool sel = false;  // a selection query: the top-K scan instead of an aggregation
+  bool dist = false;  // a SELECT DISTINCT: the presence-bitmap scan (dist_dense()) or the COUNT-only hash plan
+  bool dist_dense() const { return dist && r->dist_kind != 0; }
   pinot_amd_result* r = nullptr;
   bool restaged = false;  // raw_keys staged an expression twin (the segments' generations moved)
   // the effective query (raw_keys)
@@ -4453,6 +4538,7 @@ struct PlanBuild {
   int64_t lds_arrays();
 
   int raw_keys();
+  bool dictionary_only();
   int lanes();
   int leaves();
   int keys_probe();
@@ -4599,6 +4685,24 @@ int PlanBuild::raw_keys() {
     }
   }
   return 0;
+}
+
+// DictionaryBasedDistinctOperator's case: one distinct column, dictionary-encoded or sorted in every segment (its
+// own dictionary, not a derived twin's), and no filter. The operator reads min(LIMIT, cardinality) dictionary values
+// per segment and reports that many docs scanned.
+bool PlanBuild::dictionary_only() {
+  if (qq->group_by.size() != 1 || !qq->preds.empty() || qq->key_tf.count(qq->group_by[0]) ||
+      qq->exprs.count(qq->group_by[0]))
+    return false;
+  int64_t scanned = 0;
+  for (auto* s : segs) {
+    const Column& c = *s->cols.at(qq->group_by[0]);
+    if (c.enc == ENC_RAW) return false;
+    scanned += std::min<int64_t>(qq->distinct_limit, c.card);
+  }
+  r->dist_dict = true;
+  r->dist_dict_matched = scanned;
+  return true;
 }
 
 // Filter lanes (FilteredGroupByOperator's swim-lanes, AggregationFunctionUtils.buildFilteredAggregationInfos:407-420):
@@ -4843,6 +4947,14 @@ int PlanBuild::keys_probe() {
   r->srv_trim_threshold = Q.trim_threshold;
   r->srv_final = Q.server_final;
   r->srv_sort_threshold = Q.sort_agg_threshold;
+  if (dist) {
+    // DistinctTable knows only its LIMIT: no numGroupsLimit, no trim sizes. A hash plan's groups go through the
+    // ordered table path keeping exactly LIMIT rows (server_trim keeps LIMIT under serverReturnFinalResult)
+    r->distinct = true;
+    r->dist_limit = Q.distinct_limit;
+    r->srv_limit = Q.distinct_limit;
+    r->srv_final = 1;
+  }
   {  // QueryContext.isSameOrderAndGroupByColumns: the ORDER BY expressions, as a set, are the GROUP BY ones
     std::vector<bool> seen(Q.group_by.size(), false);
     bool only_keys = !Q.order_by.empty();
@@ -4901,7 +5013,7 @@ int PlanBuild::keys_probe() {
       for (auto& g : Q.group_by) ks *= (double)std::max(segs[si]->cols.at(g)->card, 1);
       b = std::min(b, ks);
       seg_bound[si] = (int64_t)b;
-      limit_possible |= seg_bound[si] >= Q.num_groups_limit;
+      limit_possible |= seg_bound[si] >= Q.num_groups_limit && !dist;  // (numGroupsLimit does not apply to DISTINCT)
     }
     // The key space alone allows numGroupsLimit groups somewhere: bound each segment by its matching
     // docs too (a segment's groups <= its matching docs). Counted once at plan time by a filter-only
@@ -5081,6 +5193,35 @@ int PlanBuild::plan_kind() {
   const int64_t dense_cap = std::min<int64_t>(env_i64("PINOT_AMD_DENSE_MAX_KEYS", (int64_t)1 << 28), (int64_t)1 << 31);
   if (filter_only) {
     r->kind = PLAN_FILTER;
+  } else if (dist) {
+    // SELECT DISTINCT: a presence bitmap over the whole key space up to 2^31 keys (256 MiB of bits; kernel keys
+    // are 32-bit), its table kind chosen in kernel_choices; beyond that, or when told to, the COUNT-only hash plan
+    const bool want_hash = env_is("PINOT_AMD_GROUP_PLAN", "hash") || env_is("PINOT_AMD_DISTINCT_PLAN", "hash");
+    if (!want_hash && dense_keys <= (double)((int64_t)1 << 31)) {
+      r->kind = PLAN_DENSE;
+      r->dist_kind = JitPlan::DISTINCT_HBM;
+      // the bit index: the ORDER BY columns most significant in their order (first occurrence of each, DESC
+      // flipped), then the other columns from the last to the first -- the tie rule, ascending dense key
+      std::vector<std::pair<int, int>> ocols;
+      for (const auto& ob : r->srv_order)
+        if (std::none_of(ocols.begin(), ocols.end(), [&](const std::pair<int, int>& c) { return c.first == ob.index; }))
+          ocols.push_back({ob.index, ob.asc});
+      if (!ocols.empty()) {
+        for (size_t j = Q.group_by.size(); j-- > 0;)
+          if (std::none_of(ocols.begin(), ocols.end(), [&](const std::pair<int, int>& c) { return c.first == (int)j; }))
+            ocols.push_back({(int)j, 1});
+        int64_t run = 1;
+        for (size_t o = ocols.size(); o-- > 0;) {
+          const int j = ocols[o].first;
+          const int64_t size = (int64_t)std::max<size_t>(r->keys[j]->size(), 1);
+          r->dist_ord.insert(r->dist_ord.begin(),
+                             JitPlan::OrdCol{std::max<int64_t>(r->key_stride[j], 1), size, run, ocols[o].second ? 0 : 1});
+          run *= size;
+        }
+      }
+    } else {
+      r->kind = PLAN_HASH;
+    }
   } else if (Q.group_by.empty()) {
     r->kind = PLAN_DENSE;
   } else if (limit_possible && dense_keys <= (double)dense_cap && !env_is("PINOT_AMD_GROUP_PLAN", "hash") &&
@@ -5289,6 +5430,22 @@ int PlanBuild::hash_sizes() {
     r->nbatches = b + 1;
     r->sel_ngroups = b + 1;
   }
+  if (dist_dense()) {
+    // a bitmap plan without ORDER BY stops once LIMIT rows are held: the same launch groups (run_distinct)
+    r->sel_ngroups = 1;
+    if (Q.order_by.empty()) {
+      int b = 0, left = 1;
+      for (int si = 0; si < n; ++si) {
+        seg_batch[si] = b;
+        if (--left == 0 && si + 1 < n) {
+          ++b;
+          left = 1 << std::min(b, 20);
+        }
+      }
+      r->nbatches = b + 1;
+      r->sel_ngroups = b + 1;
+    }
+  }
   return 0;
 }
 
@@ -5439,7 +5596,23 @@ int PlanBuild::kernel_choices() {
   }
   lds_bytes = (int64_t)q.nacc * std::max<int64_t>(num_keys, 1) * 8;
   hash_lds_bytes = 0;  // hash plans: the LDS first level (JitPlan::hash_lds)
-  if (r->kind == PLAN_DENSE && q.nacc > 0) {
+  if (dist_dense()) {
+    // the bitmap's table kind by its size: a 256-thread block's LDS share (40 KiB: 327 680 bits), one CU-wide
+    // block's LDS, else HBM; PINOT_AMD_DISTINCT_PLAN=lds|wide|hbm pins it (tests) where the bitmap fits
+    const int64_t bytes = jit_distinct_lds_words(num_keys) * 8;
+    int kind = bytes <= 40 * 1024 ? JitPlan::DISTINCT_LDS : bytes <= lds_max ? JitPlan::DISTINCT_WIDE : JitPlan::DISTINCT_HBM;
+    if (env_is("PINOT_AMD_DISTINCT_PLAN", "hbm")) kind = JitPlan::DISTINCT_HBM;
+    else if (env_is("PINOT_AMD_DISTINCT_PLAN", "wide") && bytes <= lds_max) kind = JitPlan::DISTINCT_WIDE;
+    else if (env_is("PINOT_AMD_DISTINCT_PLAN", "lds") && bytes <= 40 * 1024) kind = JitPlan::DISTINCT_LDS;
+    r->dist_kind = kind;
+    base.distinct = kind;
+    base.dist_ord = r->dist_ord;
+    base.dist_read = env_is("PINOT_AMD_DISTINCT_LDS_READ", "1");
+    base.aggregate = false;
+    if (kind == JitPlan::DISTINCT_WIDE) base.scan_nsub = kPartSub;
+    lds_bytes = kind == JitPlan::DISTINCT_HBM ? 0 : bytes;
+  }
+  if (r->kind == PLAN_DENSE && q.nacc > 0 && !dist) {
     const int64_t min_grid = std::max<int64_t>(1, std::min<int64_t>(cus, all_tiles / kPartSub));
     set_narrow((__int128)((all_tiles + min_grid - 1) / min_grid) * kTileDocs);
     lds_bytes = lds_arrays() * std::max<int64_t>(num_keys, 1) * 8;
@@ -5595,7 +5768,7 @@ int PlanBuild::select_plan() {
   // (a partitioned plan qualifies too: when its filter keeps few docs, the gather adds them straight into
   // the HBM table, where the partitioned plan would hand over to a fused direct-atomic scan of every row)
   // (filtered aggregations: neither the selection vector nor the filter gate carries a lane mask)
-  const bool sel_eligible = !filter_only && q.nacc > 0 && np > 0 && nlanes == 1 && !r->trim && !r->admit && !r->seg_trim &&
+  const bool sel_eligible = !filter_only && !dist_dense() && q.nacc > 0 && np > 0 && nlanes == 1 && !r->trim && !r->admit && !r->seg_trim &&
                             (r->kind == PLAN_DENSE || r->kind == PLAN_HASH || r->kind == PLAN_PARTITIONED) &&
                             !env_is("PINOT_AMD_SELECT_PARTITIONED", base.partitioned ? "0" : "-") &&
                             !(sel_env && !strcmp(sel_env, "never"));
@@ -5695,7 +5868,7 @@ int PlanBuild::select_plan() {
   // Q4.1 (1.075 -> 1.038 ms; Q1.1 0.641 -> 0.790, Q3.1 0.852 -> 1.053: profiles/r05/sweep_ssb_fgate.txt) --
   // these scans run near the HBM rate already, and the gate's one tile per step and a-tile-ahead filter cost
   // more issue than the skipped sectors save.
-  if (!base.select && r->kind == PLAN_DENSE && !base.partitioned && !r->admit && !filter_only && q.nacc > 0 && np > 0 &&
+  if (!base.select && r->kind == PLAN_DENSE && !base.partitioned && !r->admit && !filter_only && !dist && q.nacc > 0 && np > 0 &&
       nlanes == 1 && (env_is("PINOT_AMD_FILTER_GATE", "1") || env_is("PINOT_AMD_FILTER_GATE", "auto"))) {
     bool ok = true;  // docId-bitset leaves gate through the inverted-index path instead
     for (size_t k = 0; k < order.size() && ok; ++k)
@@ -6339,7 +6512,7 @@ int PlanBuild::plan_launch(size_t li) {
   }
   if (int rc = launch_helper_passes(lb)) return rc;
   L.scan_nsub = jp.partitioned ? 1 : jp.scan_nsub;
-  L.shmem = jp.lds && !jp.partitioned ? (size_t)lds_bytes : jp.hash_lds ? (size_t)hash_lds_bytes : 0;
+  L.shmem = (jp.lds && !jp.partitioned) || jp.distinct ? (size_t)lds_bytes : jp.hash_lds ? (size_t)hash_lds_bytes : 0;
   for (const JitLeaf& jl : jp.leaves) L.shmem_sets += (size_t)jl.lds_words * 4;
   {  // LDS accept tables: one per (clause, column) mask group with a lookup table (jit.cpp's layout)
     std::vector<std::pair<int, int>> groups;
@@ -6537,6 +6710,8 @@ int PlanBuild::alloc_buffers() {
         if (int rc = r->ss_hist.alloc((size_t)maxnb * 256 * 4)) return rc;
       }
     }
+  } else if (dist_dense()) {  // the presence bitmap instead of a table (+ a word: compact_slots' convention)
+    if (int rc = r->dist_bits.alloc((size_t)((num_keys + 63) / 64 + 1) * 8)) return rc;
   } else {
     if (int rc = r->acc.alloc((size_t)std::max(q.nacc, 1) * (size_t)std::max<int64_t>(num_keys, 1) * 8)) return rc;
   }
@@ -6731,6 +6906,7 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
   b.stream = stream;
   b.filter_only = filter_only;
   b.sel = sel;
+  b.dist = !filter_only && qq->distinct;
   b.r = r;
   g_tl_expr_kernel_ms = 0;
   if (int rc = b.raw_keys()) return rc;
@@ -6748,6 +6924,17 @@ static int execute_impl(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, 
   clk.mark("leaves");
   if (int rc = b.keys_probe()) return rc;
   clk.mark("keys_probe");
+  if (b.dist && b.dictionary_only()) {
+    // DictionaryBasedDistinctOperator: the answer is read off the merged dictionary (compact_distinct); no plan
+    if (int rc = r->matched.alloc(3 * sizeof(unsigned long long))) return rc;
+    HIP_OK(hipEventCreate(&r->ev0));
+    HIP_OK(hipEventCreate(&r->ev1));
+    if (int rc = run_plan(r)) return rc;
+    clk.mark("launch");
+    r->plan_bytes = g_tl_alloc_bytes - alloc0;
+    *out = res.release();
+    return 0;
+  }
   // Pinot admits groups across the lanes in the iteration order of a HashMap<FilterContext, ...>
   // (AggregationFunctionUtils.java:407, 448): once a segment can reach numGroupsLimit its result is unspecified
   if (b.nlanes > 1 && b.limit_possible)
@@ -6996,8 +7183,28 @@ static int execute_distinct(pinot_amd_query* qq, pinot_amd_segment* const* segs_
   return 0;
 }
 
+// what pinot_amd_query_set_distinct allows beside it (DistinctPlanNode takes the distinct expressions, the filter,
+// ORDER BY and LIMIT): checked before anything touches a segment or the device
+static int check_distinct_query(const pinot_amd_query& Q) {
+  if (Q.group_by.empty()) return fail(PINOT_AMD_EINVAL, "execute: a DISTINCT query without a distinct column");
+  if (!Q.aggs.empty()) return fail(PINOT_AMD_EINVAL, "execute: a DISTINCT query takes no aggregation");
+  if (!Q.sel_cols.empty() || !Q.sel_order.empty())
+    return fail(PINOT_AMD_EINVAL, "execute: a DISTINCT query takes no selection column");
+  for (const auto& ob : Q.order_by)
+    if (ob.kind != 0) return fail(PINOT_AMD_EINVAL, "execute: a DISTINCT query orders by its distinct columns only");
+  if (Q.set_result_limit || Q.set_server_options || Q.set_segment_trim)
+    return fail(PINOT_AMD_EINVAL, "execute: a DISTINCT query takes its LIMIT from pinot_amd_query_set_distinct, not %s",
+                Q.set_result_limit ? "set_result_limit" : Q.set_server_options ? "set_server_options" : "set_segment_trim");
+  if (!Q.key_space.empty())
+    return fail(PINOT_AMD_EUNSUPPORTED, "execute: DISTINCT with an installed key space (column %s): no multi-GPU merge of "
+                                        "DISTINCT results", Q.key_space.begin()->first.c_str());
+  return 0;
+}
+
 int pinot_amd_execute(pinot_amd_query* qq, pinot_amd_segment* const* segs_in, int32_t n, void* stream,
                       pinot_amd_result** out) {
+  if (qq && qq->distinct)
+    if (int rc = check_distinct_query(*qq)) return rc;
   if (qq && qq->filtered())
     for (size_t ai = 0; ai < qq->aggs.size(); ++ai)
       if (is_child_agg(qq->aggs[ai].type))
@@ -7237,6 +7444,10 @@ int pinot_amd_result_num_docs_matched(pinot_amd_result* r, int64_t* h_out) {
     *h_out = r->sel_matched;
     return 0;
   }
+  if (r->distinct && r->dist_dict) {  // what DictionaryBasedDistinctOperator reports (LIMIT 0 reads nothing)
+    *h_out = r->dist_limit == 0 ? 0 : r->dist_dict_matched;
+    return 0;
+  }
   std::vector<unsigned long long> c;
   if (int rc = read_counters(r, &c)) return rc;
   if (int rc = verify_partitioned(r, c)) return rc;
@@ -7265,6 +7476,7 @@ int pinot_amd_result_algorithmic_bytes(pinot_amd_result* r, double* h_bytes) {
   for (size_t li = 0; li < r->launches.size(); ++li) {
     const Launch& L = r->launches[li];
     if (r->topk && (r->sel_k == 0 || (r->sel_keys.empty() && L.batch >= r->sel_groups_run))) continue;  // not launched
+    if (r->dist_own() && L.batch >= r->sel_groups_run) continue;  // a DISTINCT that stopped early (or ran nothing)
     if (L.select) {  // filter columns of every doc, the vector written and read, the gathered columns
       const double m = (double)c[3 * li];
       b += L.filter_bytes + m * (16.0 + L.value_bpr);
@@ -7313,6 +7525,17 @@ static std::string kernel_info_of(pinot_amd_result* r) {
     size_t ran = 0;
     for (const auto& L : r->launches) ran += !(r->sel_keys.empty() && L.batch >= r->sel_groups_run);
     if (r->sel_k == 0) ran = 0;
+    if (ran != 1) info += " x" + std::to_string(ran);
+    return info;
+  }
+  if (r->distinct && r->dist_dict) return "distinct-dictionary";
+  if (r->dist_own()) {  // a bitmap plan (" xN": the launches the last execution ran), or LIMIT 0 on any plan
+    info = r->dist_kind == JitPlan::DISTINCT_LDS    ? "jit-distinct-lds"
+           : r->dist_kind == JitPlan::DISTINCT_WIDE ? "jit-distinct-wide"
+           : r->dist_kind == JitPlan::DISTINCT_HBM  ? "jit-distinct-hbm"
+                                                    : "jit-hash";
+    size_t ran = 0;
+    for (const auto& L : r->launches) ran += L.batch < r->sel_groups_run;
     if (ran != 1) info += " x" + std::to_string(ran);
     return info;
   }
@@ -7462,7 +7685,59 @@ static int cacc_stride(const pinot_amd_result* r) {
 }
 static const MergedKeyColumn* distinct_dictionary(const pinot_amd_result* r, int32_t agg_index);
 
+// A SELECT DISTINCT result's rows, as groups in result order (ckeys: the dense key of each row, so the group-by
+// fetch decodes them; one zero accumulator word per row). Bitmap plans: the first LIMIT set bits (counted, then
+// compacted up to LIMIT on the device), each bit index decoded back to the columns' merged ids -- digit by digit
+// of dist_ord's mixed radix, a DESC column's digit flipped back -- and re-weighted with the key strides. The
+// dictionary-only answer: the merged dictionary's first LIMIT ids, its last LIMIT descending under ORDER BY DESC.
+static int compact_distinct(pinot_amd_result* r) {
+  if (r->compacted) return 0;
+  hipStream_t st = r->stream;
+  r->ckeys.clear();
+  int64_t keep = 0;
+  if (r->dist_limit == 0) {
+  } else if (r->dist_dict) {
+    const int64_t size = (int64_t)r->keys[0]->size();
+    keep = std::min(r->dist_limit, size);
+    const bool desc = !r->srv_order.empty() && !r->srv_order[0].asc;
+    for (int64_t i = 0; i < keep; ++i) r->ckeys.push_back((uint64_t)(desc ? size - 1 - i : i));
+  } else {
+    const int64_t nbits = r->q.num_keys;
+    if (int rc = r->c_counts.ensure((size_t)compact_num_chunks(nbits) * 8)) return rc;
+    if (int rc = r->c_total.ensure(8)) return rc;
+    HIP_OK(launch_bitset_count((const uint64_t*)r->dist_bits.p, nbits, (int64_t*)r->c_counts.p, (int64_t*)r->c_total.p, st));
+    int64_t total = 0;
+    HIP_OK(hipMemcpyAsync(&total, r->c_total.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    keep = std::min(r->dist_limit, total);
+    std::vector<uint32_t> idx((size_t)keep);
+    if (keep > 0) {
+      if (int rc = r->c_idx.ensure((size_t)keep * 4)) return rc;
+      HIP_OK(launch_bitset_compact_limit((const uint64_t*)r->dist_bits.p, nbits, (const int64_t*)r->c_counts.p, keep,
+                                         (uint32_t*)r->c_idx.p, st));
+      HIP_OK(hipMemcpyAsync(idx.data(), r->c_idx.p, (size_t)keep * 4, hipMemcpyDeviceToHost, st));
+      HIP_OK(hipStreamSynchronize(st));
+    }
+    r->ckeys.resize((size_t)keep);
+    for (int64_t g = 0; g < keep; ++g) {
+      const int64_t o = (int64_t)idx[(size_t)g];
+      int64_t key = r->dist_ord.empty() ? o : 0;
+      for (const JitPlan::OrdCol& c : r->dist_ord) {
+        const int64_t d = (o / c.ostride) % c.size;
+        key += (c.flip ? c.size - 1 - d : d) * c.stride;
+      }
+      r->ckeys[(size_t)g] = (uint64_t)key;
+    }
+  }
+  r->ngroups = keep;
+  r->cacc.assign((size_t)keep * (size_t)std::max(r->q.nacc, 1), 0);
+  r->srv_trimmed = false;
+  r->compacted = true;
+  return 0;
+}
+
 static int compact_groups(pinot_amd_result* r) {
+  if (r->dist_own()) return compact_distinct(r);
   if (r->dc && r->dc->children.size())  // a failed self-check of a value-set query voids every read
     for (DistinctFold::Child& ch : r->dc->children)
       if (ch.r->check_failed) return fail(PINOT_AMD_EINVAL, "%s", ch.r->check_msg.c_str());
@@ -7823,6 +8098,7 @@ int pinot_amd_result_fetch(pinot_amd_result* r, int64_t cap, int64_t* h_keys, do
 int pinot_amd_result_fetch_intermediate(pinot_amd_result* r, int64_t cap, double* h_pairs, int64_t* h_num_fetched) {
   if (!r || cap < 0 || !h_pairs || !h_num_fetched) return fail(PINOT_AMD_EINVAL, "fetch_intermediate: bad arguments");
   if (r->topk) return fail(PINOT_AMD_EINVAL, "fetch_intermediate: a selection result has rows (pinot_amd_result_fetch_rows)");
+  if (r->distinct) return fail(PINOT_AMD_EINVAL, "fetch_intermediate: a DISTINCT result has no aggregations");
   if (int rc = no_throw("fetch_intermediate", [&] { return compact_groups(r); })) return rc;
   if (r->ngroups > cap)
     return fail(PINOT_AMD_EOVERFLOW, "fetch_intermediate: %lld groups exceed capacity %lld", (long long)r->ngroups,
@@ -7928,6 +8204,7 @@ int pinot_amd_result_accumulators(pinot_amd_result* r, int32_t* h_num_slots, int
                                   void** h_slot_ptrs, int32_t* h_slot_ops) {
   if (!r || !h_num_slots || !h_num_key_slots) return fail(PINOT_AMD_EINVAL, "accumulators: bad arguments");
   if (r->topk) return fail(PINOT_AMD_EUNSUPPORTED, "accumulators: a selection result has no accumulators");
+  if (r->distinct) return fail(PINOT_AMD_EUNSUPPORTED, "accumulators: a DISTINCT result has no accumulators");
   if (r->dc) return fail(PINOT_AMD_EUNSUPPORTED, "accumulators: a DISTINCTCOUNT result's value sets merge by union");
   if (r->kind == PLAN_HASH || r->merged)
     return fail(PINOT_AMD_EUNSUPPORTED, "accumulators: hash-table (and merged) results merge by value "
@@ -7996,6 +8273,7 @@ int pinot_amd_result_export_groups(pinot_amd_result* r, uint64_t* d_keys, uint64
   if (!r || !h_key_words || !h_num_acc || !h_num_groups || cap < 0)
     return fail(PINOT_AMD_EINVAL, "export_groups: bad arguments");
   if (r->topk) return fail(PINOT_AMD_EUNSUPPORTED, "export_groups: a selection result has no groups");
+  if (r->distinct) return fail(PINOT_AMD_EUNSUPPORTED, "export_groups: a DISTINCT result is not merged across devices");
   if (r->dc) return fail(PINOT_AMD_EUNSUPPORTED, "export_groups: a DISTINCTCOUNT result's value sets merge by union");
   return no_throw("export_groups", [&]() -> int {
     if (r->num_group_by == 0 || r->q.nacc == 0)
@@ -8030,6 +8308,7 @@ int pinot_amd_result_merge_groups(pinot_amd_result* r, const uint64_t* d_keys, c
                                   void* stream) {
   if (!r || n < 0 || (n > 0 && (!d_keys || !d_acc))) return fail(PINOT_AMD_EINVAL, "merge_groups: bad arguments");
   if (r->topk) return fail(PINOT_AMD_EUNSUPPORTED, "merge_groups: a selection result has no groups");
+  if (r->distinct) return fail(PINOT_AMD_EUNSUPPORTED, "merge_groups: a DISTINCT result is not merged across devices");
   if (r->dc) return fail(PINOT_AMD_EUNSUPPORTED, "merge_groups: a DISTINCTCOUNT result's value sets merge by union");
   return no_throw("merge_groups", [&]() -> int {
     if (r->num_group_by == 0 || r->q.nacc == 0)

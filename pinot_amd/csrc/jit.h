@@ -211,7 +211,22 @@ struct JitPlan {
   int topk_rows = 0;  // records the LDS buffer holds: a power of two, >= 512
   struct TopkField { int slot; int desc; };
   std::vector<TopkField> topk_key;
+  // SELECT DISTINCT (DistinctOperator / DistinctTable): the filter, then per matching doc one presence bit -- no
+  // accumulator, no COUNT cell. The bit index is the row's rank in the result order: a mixed radix over the group
+  // columns' merged ids, dist_ord's columns most significant first (the ORDER BY columns in their order, a DESC
+  // column's id flipped, then the remaining columns as the tie rule -- ascending dense key -- orders them); empty:
+  // the dense key itself. The bitmap of num_keys bits is the kernel's `acc` argument. distinct = DISTINCT_LDS: a
+  // block-private LDS bitmap in 256-thread blocks, DISTINCT_WIDE: in one CU-wide block (scan_nsub = kPartSub), both
+  // zeroed at block start and OR-ed into the HBM bitmap once per block (non-zero words only); DISTINCT_HBM: the HBM
+  // bitmap directly, a load before the atomic (as the segment trim's presence pass). dist_read: the LDS kinds test
+  // the bit before the LDS atomic too (a measurement knob).
+  enum { DISTINCT_NONE = 0, DISTINCT_LDS = 1, DISTINCT_WIDE = 2, DISTINCT_HBM = 3 };
+  int distinct = DISTINCT_NONE;
+  bool dist_read = false;
+  std::vector<OrdCol> dist_ord;
 };
+// 64-bit words of a distinct plan's LDS bitmap (an even count: what follows it in LDS stays 16-byte aligned)
+inline int64_t jit_distinct_lds_words(int64_t num_keys) { return ((num_keys + 63) / 64 + 1) & ~(int64_t)1; }
 // 64-bit words of a top-K record: the key fields, the docId (32 bits) and room for the segment tag (32 bits); 0 when
 // the key exceeds two words
 int jit_topk_words(const JitPlan& p);

@@ -81,6 +81,9 @@ hipError_t launch_bitset_count(const uint64_t* bits, int64_t num_docs, int64_t* 
                                hipStream_t st);
 hipError_t launch_bitset_compact(const uint64_t* bits, int64_t num_docs, const int64_t* d_chunk_offsets,
                                  int32_t* out, hipStream_t st);
+// ... stopped at the first `limit` set bits (out holds min(limit, set bits) ascending indices)
+hipError_t launch_bitset_compact_limit(const uint64_t* bits, int64_t num_bits, const int64_t* d_chunk_offsets,
+                                       int64_t limit, uint32_t* out, hipStream_t st);
 hipError_t launch_expand_jobs(const void* d_jobs, int32_t njobs, int64_t total_items, hipStream_t st);
 hipError_t launch_roaring_select(const void* d_jobs, const void* d_fs, int32_t nfs, int64_t total_items, const void* d_segs,
                                  int32_t nleaves, int32_t nclauses, unsigned long long* sel_entries,

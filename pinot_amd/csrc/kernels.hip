@@ -1528,6 +1528,38 @@ __global__ void bitset_compact_kernel(const uint64_t* bits, int64_t nwords, cons
   }
 }
 
+// The same compaction stopped at `limit` set bits (a SELECT DISTINCT's first LIMIT rows of its presence bitmap): a
+// chunk whose first set bit already ranks past the limit exits at once, the chunk holding the limit-th bit stops
+// writing there. Indices are unsigned (bitmaps of up to 2^31 bits).
+__global__ void bitset_compact_limit_kernel(const uint64_t* bits, int64_t nwords, const int64_t* chunk_offsets,
+                                            int64_t limit, uint32_t* out) {
+  __shared__ int64_t wtot[kBlock / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t base = (int64_t)blockIdx.x * kCompactWords;
+  int64_t off = chunk_offsets[blockIdx.x];
+  for (int step = 0; step < kCompactWords && off < limit; step += kBlock) {  // (off is block-uniform)
+    const int64_t w = base + step + threadIdx.x;
+    const uint64_t word = w < nwords ? bits[w] : 0ull;
+    const int cnt = __popcll(word);
+    int incl = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int y = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += y;
+    }
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    int64_t wave_off = 0;
+    for (int i = 0; i < wave; ++i) wave_off += wtot[i];
+    int64_t pos = off + wave_off + incl - cnt;
+    for (uint64_t x = word; x && pos < limit; x &= x - 1) out[pos++] = (uint32_t)(w * 64 + __builtin_ctzll(x));
+    int64_t step_total = 0;
+    for (int i = 0; i < kBlock / 64; ++i) step_total += wtot[i];
+    off += step_total;
+    __syncthreads();
+  }
+}
+
 // Inverted index expansion: one block per (dictId, container) entry of a container directory
 // built at staging time. Sets the container's docs in the dense bitset (atomicOr: containers of
 // different dictIds share 64-bit words).
@@ -2623,6 +2655,16 @@ hipError_t launch_bitset_compact(const uint64_t* bits, int64_t num_docs, const i
   const int64_t nw = (num_docs + 63) / 64;
   const int64_t nc = compact_num_chunks(num_docs);
   hipLaunchKernelGGL(bitset_compact_kernel, dim3((unsigned)nc), dim3(kBlock), 0, st, bits, nw, d_chunk_offsets, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_bitset_compact_limit(const uint64_t* bits, int64_t num_bits, const int64_t* d_chunk_offsets,
+                                       int64_t limit, uint32_t* out, hipStream_t st) {
+  const int64_t nw = (num_bits + 63) / 64;
+  const int64_t nc = compact_num_chunks(num_bits);
+  if (nc <= 0 || limit <= 0) return hipSuccess;
+  hipLaunchKernelGGL(bitset_compact_limit_kernel, dim3((unsigned)nc), dim3(kBlock), 0, st, bits, nw, d_chunk_offsets,
+                     limit, out);
   return hipGetLastError();
 }
 

@@ -200,6 +200,7 @@ def merge_result(result, scratch=None, group=None, stream=None, gather_max_bytes
     import torch.distributed as dist
     _refuse_filtered_aggregations(getattr(result, "qc", None))
     _refuse_expressions(getattr(result, "qc", None))
+    _refuse_distinct(getattr(result, "qc", None))
     _refuse_multi_value(getattr(result, "qc", None), result)
     cur = torch.cuda.current_stream() if torch.cuda.is_available() else None
     if stream is not None and cur is not None:
@@ -369,6 +370,7 @@ def merge_groups(qc, groups: dict, group=None) -> dict:
     from .query import merge_partial
     _refuse_filtered_aggregations(qc)
     _refuse_expressions(qc)
+    _refuse_distinct(qc)
     _refuse_multi_value(qc)
     world = dist.get_world_size(group)
     parts = [None] * world
@@ -414,6 +416,13 @@ def _refuse_expressions(qc) -> None:
     (pinot_amd_query_set_group_key_values: EUNSUPPORTED) and no tested cross-rank merge."""
     if qc is not None and getattr(qc, "expressions", None) is not None and qc.expressions():
         raise ValueError(f"arithmetic expressions ({', '.join(qc.expressions())}) are not covered by the cross-rank merge")
+
+
+def _refuse_distinct(qc) -> None:
+    """SELECT DISTINCT runs on one GPU: its presence bitmaps would merge by OR once key spaces are installed, which
+    the library does not take for a distinct query (pinot_amd_query_set_group_key_values: EUNSUPPORTED)."""
+    if qc is not None and getattr(qc, "distinct", False):
+        raise ValueError("a SELECT DISTINCT query is not covered by the cross-rank merge")
 
 
 def _refuse_multi_value(qc, result=None) -> None:

@@ -720,6 +720,93 @@ class SelectionResult:
             pass
 
 
+class DistinctResult:
+    """Rows of one executed distinct query (SELECT DISTINCT columns [WHERE] [ORDER BY ...] LIMIT n).
+
+    columns: the distinct columns in select-list order. rows(): at most LIMIT distinct rows in the ORDER BY's order
+    (ties by ascending global group key); without ORDER BY the first LIMIT rows held, in ascending global key order.
+    Values are typed like group keys (JavaDouble for FLOAT / DOUBLE); STRING values are resolved for the returned
+    rows only."""
+
+    def __init__(self, handle, qc: QueryContext, columns: List[str], types: List[str]):
+        self._h = handle
+        self.qc = qc
+        self.columns = columns
+        self._types = types
+
+    def execute_again(self, stream=None) -> None:
+        check(lib().pinot_amd_execute_again(self._h, _stream_handle(stream)), "execute_again")
+
+    def num_docs_matched(self) -> int:
+        """The docs matching the filter in the segments actually scanned (the dictionary-only answer: the sum of
+        min(LIMIT, cardinality) over the segments, as DictionaryBasedDistinctOperator reports)."""
+        out = C.c_int64()
+        check(lib().pinot_amd_result_num_docs_matched(self._h, C.byref(out)), "num_docs_matched")
+        return out.value
+
+    def kernel_info(self) -> str:
+        """'jit-distinct-lds' / '-wide' / '-hbm' (' xN' for N != 1 launches run), the hash plan's name, or
+        'distinct-dictionary'."""
+        return lib().pinot_amd_result_kernel_info(self._h).decode()
+
+    def packed_info(self) -> str:
+        return lib().pinot_amd_result_packed_info(self._h).decode()
+
+    def last_kernel_ms(self) -> float:
+        out = C.c_double()
+        check(lib().pinot_amd_result_last_kernel_ms(self._h, C.byref(out)), "last_kernel_ms")
+        return out.value
+
+    def algorithmic_bytes(self) -> float:
+        out = C.c_double()
+        check(lib().pinot_amd_result_algorithmic_bytes(self._h, C.byref(out)), "algorithmic_bytes")
+        return out.value
+
+    def plan_timing(self) -> Dict[str, float]:
+        txt = lib().pinot_amd_result_plan_timing(self._h).decode()
+        return {k: float(v) for k, v in (kv.split("=") for kv in txt.split(";") if kv)}
+
+    def fetch_arrays(self):
+        """(rows, values [rows, columns] in fetch's key encoding), in result order."""
+        L = lib()
+        ng = C.c_int64()
+        check(L.pinot_amd_result_num_groups(self._h, C.byref(ng)), "num_groups")
+        cap = max(ng.value, 1)
+        nc = len(self.columns)
+        keys = np.zeros(cap * nc, dtype=np.int64)
+        got = C.c_int64()
+        check(L.pinot_amd_result_fetch(self._h, cap, keys.ctypes.data_as(C.POINTER(C.c_int64)), None, None,
+                                       C.byref(got)), "fetch")
+        g = got.value
+        return g, keys[:g * nc].reshape(g, nc)
+
+    def rows(self) -> List[tuple]:
+        L = lib()
+        g, vals = self.fetch_arrays()
+        cols = []
+        for j, t in enumerate(self._types):
+            col = np.ascontiguousarray(vals[:, j])
+            if t == STRING:
+                names = {int(i): L.pinot_amd_result_string_key(self._h, j, int(i)).decode() for i in np.unique(col)}
+                cols.append([names[i] for i in col.tolist()])
+            elif t in (FLOAT, DOUBLE):
+                cols.append([JavaDouble(x) for x in col.view(np.float64).tolist()])
+            else:
+                cols.append(col.tolist())
+        return list(zip(*cols)) if g else []
+
+    def destroy(self) -> None:
+        if self._h:
+            lib().pinot_amd_result_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
 class ServerQueryExecutor:
     """Compiles a QueryContext and runs it over a list of HBM-resident segments.
 
@@ -811,6 +898,10 @@ class ServerQueryExecutor:
             if key_space is not None:
                 raise _lib.PinotAmdError("a selection query takes no key_space (its rows merge by value at the broker)")
             return self._execute_selection(qc, segments, stream)
+        if qc.is_distinct():
+            if key_space is not None:
+                raise _lib.PinotAmdError("a distinct query takes no key_space (there is no multi-GPU merge of its rows)")
+            return self._execute_distinct(qc, segments, stream)
         if any(a.func in VALUE_SET_FUNCS for a in qc.aggregations) and self.distinct_count == "native":
             if key_space is not None:
                 raise _lib.PinotAmdError("distinct_count='native' takes no key_space: results of several ranks merge "
@@ -864,6 +955,36 @@ class ServerQueryExecutor:
         finally:
             L.pinot_amd_query_destroy(qh)
         return SelectionResult(rh, qc, columns, [cbs[c].stored_type for c in columns])
+
+    def _execute_distinct(self, qc: QueryContext, segments: Sequence[ImmutableSegment], stream=None) -> DistinctResult:
+        """DistinctPlanNode: the distinct columns as the library's keys, the ORDER BY over them, the LIMIT."""
+        if not segments:
+            raise ValueError("no segments")
+        L = lib()
+        first = segments[0]
+        qh, names = self._compile(qc, segments)
+        try:
+            for g in qc.group_by:
+                kt = key_transform(g)
+                if kt is not None:
+                    spec = key_transform_spec(kt)
+                    check(L.pinot_amd_query_add_group_by_transform(qh, kt.column.encode(), C.byref(spec)),
+                          f"add_group_by_transform({g})")
+                    continue
+                if names.column(g) is None:
+                    raise _lib.PinotAmdError(f"unknown column {g!r} in segment {first.name}")
+                check(L.pinot_amd_query_add_group_by(qh, names.abi(g)), "add_group_by")
+            for kind, idx, asc in qc.order_by_targets():
+                check(L.pinot_amd_query_add_order_by(qh, kind, idx, 1 if asc else 0), "add_order_by")
+            check(L.pinot_amd_query_set_distinct(qh, qc.limit), "set_distinct")
+            arr = (C.c_void_p * len(segments))(*[s.handle.value for s in segments])
+            rh = C.c_void_p()
+            check(L.pinot_amd_execute(qh, arr, len(segments), _stream_handle(stream), C.byref(rh)), "execute")
+        finally:
+            L.pinot_amd_query_destroy(qh)
+        types = [LONG if key_transform(g) is not None else DOUBLE if expression(g) is not None
+                 else first.columns[g].stored_type for g in qc.group_by]
+        return DistinctResult(rh, qc, list(qc.group_by), types)
 
     @staticmethod
     def _set_key_space(qh, column: str, stored_type: str, values) -> None:

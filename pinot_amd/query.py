@@ -582,6 +582,12 @@ class QueryContext:
     offset: int = 0                     # LIMIT n OFFSET m / LIMIT m, n (the broker applies it; a server keeps offset + limit)
     # filteredAggregationsSkipEmptyGroups: with only filtered aggregations, a group exists iff some lane has a doc
     filtered_aggregations_skip_empty_groups: bool = False
+    # SELECT DISTINCT a, b ... (DistinctPlanNode): the distinct columns are group_by (= select_columns), in list order
+    distinct: bool = False
+
+    def is_distinct(self) -> bool:
+        """SELECT DISTINCT columns [WHERE] [ORDER BY] [LIMIT]: the distinct rows of the columns (DistinctPlanNode)."""
+        return self.distinct
 
     def has_filtered_aggregations(self) -> bool:
         return any(a.filter is not None for a in self.aggregations)
@@ -878,6 +884,11 @@ class _Parser:
     # -- grammar --
     def query(self) -> QueryContext:
         self.eat_kw("SELECT")
+        # SELECT DISTINCT a, b: the keyword, unless what follows makes it a column named "distinct"
+        distinct = self.kw("DISTINCT") and self.peek(1) not in (("op", ","), ("op", "(")) and \
+            not (self.peek(1)[0] == "id" and self.peek(1)[1].upper() == "FROM") and self.peek(1)[0] != "eof"
+        if distinct:
+            self.i += 1
         aggs, cols = [], []
         while True:
             tok = self.peek()
@@ -944,6 +955,20 @@ class _Parser:
                 offset = self.count("OFFSET")
         if self.peek()[0] != "eof":
             raise ValueError(f"unexpected trailing token {self.peek()}")
+        if distinct:
+            if aggs:
+                raise ValueError(f"SELECT DISTINCT takes columns, not an aggregation ({aggs[0].text})")
+            if group_by:
+                raise ValueError("SELECT DISTINCT takes no GROUP BY")
+            if "*" in cols:
+                raise ValueError("SELECT DISTINCT * is not supported: name the columns")
+            if offset:
+                raise ValueError(f"SELECT DISTINCT with OFFSET {offset} is not supported")
+            group_by = list(dict.fromkeys(cols))  # (a column listed twice is one distinct column)
+            cols = list(group_by)
+            for e, _ in order:
+                if e not in group_by:  # (both are key_item's canonical text; column names are case-sensitive)
+                    raise ValueError(f"ORDER BY {e} is not in the SELECT DISTINCT list")
         if "*" in cols and (aggs or group_by):
             raise ValueError("SELECT * takes no aggregation and no GROUP BY")
         for c in cols + [e for e, _ in order]:
@@ -951,7 +976,7 @@ class _Parser:
                 if not aggs and not group_by:
                     raise ValueError("a key transform in a selection query is not supported (only as a GROUP BY key)")
                 raise ValueError(f"{c} is not a GROUP BY key of the query")
-        return QueryContext(table, aggs, group_by, flt, order, limit, cols, offset=offset)
+        return QueryContext(table, aggs, group_by, flt, order, limit, cols, offset=offset, distinct=bool(distinct))
 
     def agg_filter(self) -> Optional[FilterContext]:
         """FILTER (WHERE <expr>) behind an aggregation call, or None."""
